@@ -24,7 +24,20 @@ probes the hash table instead).  ``--placement affine`` (actor a on rank a % N,
 mailbox a / N) lets the route be computed without registry reads; it is reported
 as a secondary figure, never as the headline.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+A plain run measures the headline alone: set-up, warm-up, the timed steps (their
+replies verified), the result line.  ``--full`` adds everything else: the
+secondary measurements (affine placement, the other deliveries / shardings /
+sizes / methods, optimus fan-out, the 1 M registry, the public API path) under
+``secondaries``, and the p50 RTT calls (``p50_rtt*`` are null without it).
+
+``--dump-outputs DIR`` writes what the last timed step of the headline returned
+to its caller -- the reply values and statuses in message order -- as
+``DIR/values.npy`` (float64) and ``DIR/status.npy`` (float32), a fixed seeded
+sample of the messages when the whole arrays would exceed 60 MB (its indices:
+``DIR/sample_index.npy``).  Requests are seeded by step and rank only, so two
+runs with the same arguments dump the replies to the same requests.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   N > 1 without torchrun: bench.py starts torch.distributed.run with N rank
   processes itself (a child process, before anything touches a GPU) and exits
   with its status.
@@ -47,7 +60,11 @@ def _parse():
     p.add_argument("--msgs-per-gpu", type=int, default=8 * 1024 * 1024, help="messages each rank sends per step")
     p.add_argument("--actors-per-gpu", type=int, default=131072)
     p.add_argument("--chunks", type=int, default=0, help="pipeline chunks per step (0 = auto)")
-    p.add_argument("--rtt-calls", type=int, default=2000)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline: the secondary measurements and the p50 RTT calls")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the replies of the last timed headline step to DIR/<name>.npy (at most 64 MB)")
+    p.add_argument("--rtt-calls", type=int, default=2000, help="with --full: synchronous Calls timed for the p50 RTT")
     p.add_argument("--cpu", action="store_true", help="gloo/CPU dry run of the same pipeline (tests)")
     p.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                    help="replay the step as a captured hipGraph (auto: single rank)")
@@ -82,12 +99,40 @@ def _parse():
                    help="the timed step's method (seqfold: the ordered stateful method -- experiments; "
                         "the headline is Calculator.Multiply)")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary (affine placement) measurement after the headline")
+                   help="with --full: skip the secondary measurements after the headline")
     p.add_argument("--comm", choices=["rccl", "ipc"], default="rccl",
                    help="N > 1 data-plane transport of the compiled DataPlane (csrc/core/dataplane.cpp): RCCL over "
                         "xGMI (one GPU per rank), or IpcComm (csrc/hip/ipc_comm.hpp: shared-memory segments) -- ipc "
                         "lets every rank share one GPU: a multi-process rehearsal, not a scaling figure")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_secondary, args.rtt_calls = True, 0
+    return args
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: all ranks' files together stay under this (the limit is 64 MB)
+
+
+def dump_outputs(path: str, val, st, rank: int, world: int) -> None:
+    """The replies a Send returned (values int64, statuses int32, message order) as
+    .npy files: whole when they fit this rank's share of DUMP_BYTES, else at a
+    fixed seeded sample of message indices (the same for every run and rank)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    M = val.numel()
+    budget = DUMP_BYTES // world
+    idx = None
+    if M * (8 + 4) > budget:
+        n = budget // (8 + 4 + 8)  # value + status + the index itself
+        idx = np.sort(np.random.RandomState(20240607).randint(0, M, size=n, dtype=np.int64))
+        np.save(os.path.join(path, f"sample_index{sfx}.npy"), idx.astype(np.float64))
+    v, s = val.cpu().numpy(), st.cpu().numpy()
+    if idx is not None:
+        v, s = v[idx], s[idx]
+    np.save(os.path.join(path, f"values{sfx}.npy"), v.astype(np.float64))
+    np.save(os.path.join(path, f"status{sfx}.npy"), s.astype(np.float32))
 
 
 def _spawn_ranks(args) -> int:
@@ -309,6 +354,7 @@ def main():
 
     host_us_per_step = [None]
     host_split = [None]  # the sorted engine's host time split (timed steps, this rank)
+    last_out = [None]  # (values, statuses) the last measured step returned
 
     def measure(table, steps, warmup, delivery=args.delivery, sharding=args.sharding, Mq=M,
                 method=METHOD_CALC_MULTIPLY, wide=False, pregen=False):
@@ -419,6 +465,7 @@ def main():
         elapsed = max_over_ranks(elapsed)
         if steps:
             verify("timed", last(warmup + steps), vt[1], vt[2], method)
+        last_out[0] = (vt[1], vt[2])
         return elapsed, ex, graph is not None
 
     def mailbox_info(ex_):
@@ -442,6 +489,8 @@ def main():
         _hang_watchdog(float(hang_s), rank)
     head_method = METHOD_SEQ_FOLD if args.method == "seqfold" else METHOD_CALC_MULTIPLY
     elapsed, ex, graphed = measure(table, args.steps, args.warmup, method=head_method)
+    if args.dump_outputs:  # before anything else reuses the reply buffers
+        dump_outputs(args.dump_outputs, *last_out[0], rank, world)
     head_host_us = host_us_per_step[0]
     head_host_split = host_split[0]
     def lookup_mode(t):

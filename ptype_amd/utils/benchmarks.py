@@ -1,5 +1,5 @@
 """Secondary measurements of ``bench.py`` (BASELINE.json configs 4 and 5, and the
-public API path), each a dict that bench.py puts under ``secondaries``.
+public API path), each a dict that ``bench.py --full`` puts under ``secondaries``.
 
 * ``registry_1m``: the 1M-actor GPU registry mirror (K5 inserts / updates /
   lookups, K5b directory build, K6 sweep scan) and its snapshot into pinned host

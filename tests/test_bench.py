@@ -39,7 +39,7 @@ SMALL = ["--steps", "2", "--warmup", "1", "--msgs-per-gpu", "20000", "--actors-p
 
 @pytest.mark.parametrize("nproc,launcher", [(1, "self"), (2, "torchrun"), (2, "self")])
 def test_bench_json_contract_cpu(nproc, launcher):
-    out = _run(nproc, ["--cpu"] + SMALL, launcher=launcher)
+    out = _run(nproc, ["--cpu", "--full"] + SMALL, launcher=launcher)
     assert REQUIRED <= set(out)
     assert out["metric"] == "messages/sec" and out["unit"] == "msg/s" and out["higher_is_better"] is True
     assert out["n_gpus"] == nproc and out["steps"] == 2 and out["warmup"] == 1 and out["scaling"] == "weak"
@@ -50,6 +50,54 @@ def test_bench_json_contract_cpu(nproc, launcher):
     assert out["secondaries"]["affine_placement"]["placement"] == "affine"
     # value is the whole-job aggregate: every rank's messages over the max rank time
     assert out["value"] == pytest.approx(20000 * nproc * 2 / (out["ms_per_step"] * 2 / 1e3), rel=1e-6)
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_replies_cpu(tmp_path):
+    """Without --full: no secondaries, no RTT calls (asked-for ones included), the
+    same headline fields.  --dump-outputs: the last timed step's replies, whole
+    (they fit), float64 values and float32 statuses, the same from run to run."""
+    import numpy as np
+
+    from ptype_amd.ops.records import STATUS_OK
+
+    dumps = []
+    for d in ("a", "b"):
+        out = _run(1, ["--cpu", "--steps", "3", "--warmup", "1", "--msgs-per-gpu", "20000", "--actors-per-gpu", "1024",
+                       "--rtt-calls", "50", "--dump-outputs", str(tmp_path / d)])
+        assert REQUIRED <= set(out) and "secondaries" not in out
+        assert out["p50_rtt_us"] is None and out["p50_rtt_local_us"] is None
+        assert out["steps"] == 3 and out["value"] == pytest.approx(20000 * 3 / (out["ms_per_step"] * 3 / 1e3), rel=1e-6)
+        assert sorted(os.listdir(tmp_path / d)) == ["status.npy", "values.npy"]
+        dumps.append((np.load(tmp_path / d / "values.npy"), np.load(tmp_path / d / "status.npy")))
+    (v0, s0), (v1, s1) = dumps
+    assert v0.dtype == np.float64 and s0.dtype == np.float32 and v0.shape == s0.shape == (20000,)
+    assert np.array_equal(v0, v1) and np.array_equal(s0, s1)
+    assert (s0 == STATUS_OK).all() and len(np.unique(v0)) > 1000  # products of random arguments, every call served
+
+
+def test_dump_outputs_samples_large_replies_within_the_size_limit(tmp_path):
+    """Replies too large to dump whole: a fixed sample (sorted indices, the same
+    for every call), values and statuses taken at it, all files under 64 MB."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    M = 6_000_000
+    val = torch.arange(M, dtype=torch.int64) * 3 - 5
+    st = (torch.arange(M, dtype=torch.int64) % 7).to(torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), val, st, 0, 1)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))
+    i = idx.astype(np.int64)
+    assert 1_000_000 < len(i) < M and (np.diff(i) >= 0).all() and i[0] >= 0 and i[-1] < M
+    assert np.array_equal(np.load(tmp_path / "a" / "values.npy"), (i * 3 - 5).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), (i % 7).astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+    bench.dump_outputs(str(tmp_path / "r"), val, st, 1, 2)  # a rank of two: its own files, half the budget
+    assert sorted(os.listdir(tmp_path / "r")) == ["sample_index_rank1.npy", "status_rank1.npy", "values_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "r" / f) for f in os.listdir(tmp_path / "r")) <= 32_000_000
 
 
 def _gpus() -> int:
@@ -66,7 +114,7 @@ def _gpus() -> int:
 def test_bench_multi_gpu(nproc):
     if _gpus() < nproc:
         pytest.skip(f"needs {nproc} GPUs (RCCL refuses two ranks on one device)")
-    out = _run(nproc, ["--steps", "3", "--warmup", "2", "--rtt-calls", "200"], timeout=900)
+    out = _run(nproc, ["--full", "--steps", "3", "--warmup", "2", "--rtt-calls", "200"], timeout=900)
     assert out["n_gpus"] == nproc and out["value"] > 0  # (the bench verifies every reply itself)
     # the N > 1 mailbox path is the sorted exchange (csrc/hip/exchange_sorted.hpp): wire-v3
     # records through padded RCCL all-to-alls at the capacity agreed two Sends earlier (or,
@@ -97,7 +145,7 @@ def test_bench_multi_process_on_one_gpu_ipc(nproc):
     next rank's dispatcher ring, and skewed (Zipf) traffic without re-sends once
     the agreement applies."""
     small = ["--msgs-per-gpu", str(1 << 18), "--actors-per-gpu", "8192", "--comm", "ipc"]
-    out = _run(nproc, ["--steps", "4", "--warmup", "3", "--rtt-calls", "200", "--no-secondary"] + small,
+    out = _run(nproc, ["--full", "--steps", "4", "--warmup", "3", "--rtt-calls", "200", "--no-secondary"] + small,
                timeout=600, launcher="self")
     c = out["config"]
     assert out["n_gpus"] == nproc and out["value"] > 0
@@ -114,8 +162,8 @@ def test_bench_force_dist_remote_rtt():
     """World 1 with the compiled DataPlane's RCCL communicator up: the multi-rank
     RTT phase (store barriers, the "next rank's" dispatcher mapped from its dma-buf
     -- here this rank's own) runs as it does at N > 1."""
-    out = _run(1, ["--force-dist", "--steps", "2", "--warmup", "1", "--rtt-calls", "200", "--no-secondary"],
-               timeout=300)
+    out = _run(1, ["--full", "--force-dist", "--steps", "2", "--warmup", "1", "--rtt-calls", "200",
+                   "--no-secondary"], timeout=300)
     assert out["rtt_error"] is None, out["rtt_error"]
     assert out["p50_rtt_remote_us"] is not None and out["p50_rtt_remote_us"] > 0
     assert out["rtt_remote_request_ring"] == "device"
@@ -188,7 +236,8 @@ def test_bench_api_send_secondary_at_n2_over_ipc():
     ranks on one GPU (IpcComm), Join -> NewClient -> Client.Send on both, replies
     verified, no host wait per Send beyond the deferred re-send resolution."""
     small = ["--msgs-per-gpu", str(1 << 18), "--actors-per-gpu", "8192", "--comm", "ipc"]
-    out = _run(2, ["--steps", "3", "--warmup", "2", "--rtt-calls", "0"] + small, timeout=600, launcher="self")
+    out = _run(2, ["--full", "--steps", "3", "--warmup", "2", "--rtt-calls", "0"] + small, timeout=600,
+               launcher="self")
     api = out["secondaries"]["api_send"]
     assert "error" not in api, api
     assert api["ranks"] == 2 and api[str(1 << 18)]["value"] > 0, api
