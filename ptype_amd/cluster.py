@@ -201,7 +201,7 @@ class Client:
     def Go(self, serviceMethod: str, args: Any, done: CallChannel | None = None):
         return self._c.go(serviceMethod, args, done)
 
-    def Send(self, batch, **kw):
+    def Send(self, batch, retries: int | None = None, retry_on=None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -210,9 +210,20 @@ class Client:
         it.  With more than one rank, a message that overflowed its region (skewed
         traffic beyond the agreed capacity) reads STATUS_OVERFLOW until its re-send
         -- at most two Sends later, or at ``Flush()`` -- writes its reply into the
-        same tensors; keep ``batch`` unchanged until then."""
+        same tensors; keep ``batch`` unchanged until then.
+
+        ``retries``: the reference's ``withRetry`` (cluster/rpc.go:107-116) on the
+        batch -- every message whose status is in ``retry_on`` (default
+        ``STATUS_FAILED``) is sent again, up to ``retries`` times, each time to the
+        next replica of the round robin, and its reply replaces the failed one.
+        Opt-in (``retries=client.cfg.retries`` for the reference's behaviour): it
+        costs a host read per Send, and a retried message runs after the rest of
+        its batch, so a batch with an ordered method is refused.  ``None``: one
+        attempt, exactly the Send above."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
+        if retries:
+            kw.update(retries=int(retries), retry_on=retry_on)
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

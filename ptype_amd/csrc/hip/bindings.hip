@@ -80,6 +80,10 @@ void launch_complete_packed(uintptr_t, int64_t, int, int, uintptr_t, int64_t, ui
                             uintptr_t, uintptr_t, uintptr_t, int64_t);
 void launch_records_to_soa(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, bool, uintptr_t);
 void launch_snapshot_copy(uintptr_t, uintptr_t, int64_t, uintptr_t);
+int64_t retry_tile();
+void launch_retry_select(uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                         uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
+void launch_retry_merge(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -249,6 +253,17 @@ PYBIND11_MODULE(_hip, m) {
         "32-B AoS request records -> SoA columns (dwordx4 copy, or MFMA byte transposition)");
   m.def("snapshot_copy", &launch_snapshot_copy, py::arg("dst"), py::arg("src"), py::arg("n16"),
         py::arg("stream"));
+
+  // ---- Send retries (retry.hip): pick the failed messages of a batch out, put their replies back
+  m.def("retry_tile", &retry_tile, "statuses per block of retry_select");
+  m.def("retry_select", &launch_retry_select, py::arg("status"), py::arg("M"), py::arg("mask"), py::arg("actor"),
+        py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("method"), py::arg("idx"), py::arg("actor_out"),
+        py::arg("a0_out"), py::arg("a1_out"), py::arg("a2_out"), py::arg("method_out"), py::arg("counts"),
+        py::arg("k_out"), py::arg("stream"),
+        "stable compaction of the messages whose status bit is set in mask: idx (ascending), the gathered rows of "
+        "every non-null column, K in k_out[0]; counts: ceil(M / retry_tile()) u32 words of workspace");
+  m.def("retry_merge", &launch_retry_merge, py::arg("val"), py::arg("st"), py::arg("M"), py::arg("idx"), py::arg("v2"),
+        py::arg("s2"), py::arg("K"), py::arg("stream"), "val[idx[j]] = v2[j], st[idx[j]] = s2[j] for j < K");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

@@ -53,7 +53,7 @@ import torch.distributed as dist
 from ..ops import batch as B
 from ..ops import raw_stream, tune
 from ..ops.packed import META_CAP, META_WORDS
-from ..ops.records import STATUS_OVERFLOW, method_ordered
+from ..ops.records import STATUS_FAILED, STATUS_OVERFLOW, method_ordered
 from ..ops.table import RegistryTable
 from ..utils import trace
 
@@ -75,6 +75,8 @@ class EpochStats:
     epochs: int = 0  # chunk epochs run (one request + one reply all-to-all each)
     wire_bytes: int = 0  # bytes this rank put on the all-to-alls (requests + replies, padded slots)
     resends: int = 0  # send_all re-send rounds
+    retries: int = 0  # send_all(retries=...) retry rounds run
+    retried: int = 0  # messages this rank ran again in them
     overflow: int = 0  # device counters (cumulative): overflowed, no-actor, handler-failed
     nomatch: int = 0
     failed: int = 0
@@ -760,7 +762,8 @@ class ActorExchange:
         return epochs, delivered
 
     # ------------------------------------------------------------------
-    def send_all(self, req: B.MsgBatch, max_epochs: int = 16, out: tuple | None = None, defer: bool = False):
+    def send_all(self, req: B.MsgBatch, max_epochs: int = 16, out: tuple | None = None, defer: bool = False,
+                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None):
         """`send` + re-send of overflowed messages until every one is delivered.
         Reads the overflow count once per epoch (a host round trip); with adaptive
         slot capacity (native engine, wire v3) skewed traffic fits in the first
@@ -774,7 +777,37 @@ class ActorExchange:
         on every rank -- and writes the replies into Send k's output tensors.  Until
         then a message that overflowed reads STATUS_OVERFLOW ("pending re-send"),
         and the batch ``req`` must stay unchanged.  No host wait on the current
-        Send."""
+        Send.
+
+        ``retries`` > 0: the reference's ``withRetry`` (cluster/rpc.go:59-116) on the
+        batch -- at most ``1 + retries`` attempts per message.  After the Send and
+        its overflow re-sends (never deferred), up to ``retries`` rounds pick the
+        messages whose status is in ``retry_on`` out of the batch on the device
+        (ops/retry.py), send them again and merge the replies into ``val`` /
+        ``st``.  A message that succeeded is never run again; one still failing
+        after the last round keeps its last status and value.  Every rank runs
+        the same number of rounds (the node-wide maximum of the counts is agreed;
+        a rank with nothing to retry joins with an empty batch); one host read
+        per round.  ``reroute``: the routed actor ids for a tensor of logical ones
+        (``ReplicaRouter.route``) -- a round's sub-batch is then built from
+        ``logical`` (the caller's logical actor ids, default ``req.actor``) and
+        routed afresh, the reference's ``c.conns.Get()`` inside the retry closure.
+        A retried message runs after the rest of its batch, so a batch that
+        carries an ordered method is refused; so is a Send under graph capture."""
+        retries = int(retries)
+        if retries < 0:
+            raise ValueError("retries >= 0")
+        if retries:
+            from ..ops import retry as R
+
+            R.retry_mask(retry_on)
+            if self._capturing:
+                raise ValueError("send_all(retries > 0) inside a captured Send: the retry rounds need a host read")
+            if R.carries_ordered(req):
+                raise ValueError("send_all(retries > 0): the batch carries an ordered method -- a retried message "
+                                 "would run after later messages to its actor and break the per-actor FIFO")
+            val, st = self._send_delivered(req, max_epochs, out)
+            return self._retry_rounds(req, val, st, max_epochs, retries, retry_on, reroute, logical)
         val, st = self.send(req, *(out or ()))
         if self._fits_for_sure():
             return val, st
@@ -846,6 +879,31 @@ class ActorExchange:
             st[idx] = s2
         return val, st
 
+    def _send_delivered(self, req, max_epochs: int, out=None):
+        """``send`` and, right away, its overflow re-send rounds."""
+        val, st = self.send(req, *(out or ()))
+        if not self._fits_for_sure():
+            self._resend_rounds(req, val, st, max_epochs, None)
+        return val, st
+
+    def _retry_rounds(self, req, val, st, max_epochs: int, retries: int, retry_on, reroute, logical):
+        from ..ops import retry as R
+
+        src = req
+        if reroute is not None and logical is not None:
+            src = B.MsgBatch(logical, req.a0, req.a1, req.a2, req.method)
+        for _ in range(retries):
+            sub, idx, K = R.select(src, st, retry_on)
+            if (self._agree_max(K) if self.world > 1 else K) == 0:
+                break
+            self.counters.retries += 1
+            self.counters.retried += K
+            if reroute is not None:  # the next replica of the round robin (K = 0: nothing to route)
+                sub = B.MsgBatch(reroute(sub.actor) if K else sub.actor, sub.a0, sub.a1, sub.a2, sub.method)
+            v2, s2 = self._send_delivered(sub, max_epochs)
+            R.merge(val, st, idx, v2, s2)
+        return val, st
+
     def _fits_for_sure(self) -> bool:
         """Whether the last native send provably overflowed no slot on any rank: its
         capacity was sized from the agreed busiest (rank, destination) bucket of the
@@ -885,7 +943,7 @@ class ActorExchange:
     def stats(self) -> EpochStats:
         c = self.counters
         s = EpochStats(sent=c.sent, epochs=c.epochs, wire_bytes=c.wire_bytes, resends=c.resends,
-                       pump_sealed=c.pump_sealed)
+                       retries=c.retries, retried=c.retried, pump_sealed=c.pump_sealed)
         s.nomatch -= c.pump_sealed
         for b in self.bufs:
             w = B.ws_stats(b.ws).tolist()

@@ -335,13 +335,26 @@ class DeviceRuntime:
         la = local_addr if local_addr is not None else (self._addr[0] if getattr(self, "_addr", None) else "")
         return ReplicaRouter(service, self.world0, la, max_connections, kv=self._kv)
 
-    def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None):
+    def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
+             retries: int | None = None, retry_on=None):
         """Batched Send: every message to its actor anywhere in the node and the
         replies back in message order.  Collective across the process group.
         Registry changes seen since the last Send are applied first.  With an
         elastic group a rank failure is recovered here (module docstring).
         ``router``: a replicated service's ReplicaRouter -- the batch's logical
-        actor ids are routed to the selected replicas, round robin."""
+        actor ids are routed to the selected replicas, round robin.
+        ``retries``: up to that many further attempts of every message whose status
+        is in ``retry_on`` (default STATUS_FAILED), each through ``router`` again --
+        the reference's ``withRetry`` (``ActorExchange.send_all``).  None or 0: one
+        attempt, no retry work at all."""
+        rkw = {}
+        if retries:
+            if not resend_overflow:
+                raise ValueError("send(retries > 0) runs after the overflow re-sends: resend_overflow=False excludes it")
+            rkw = {"retries": int(retries), "reroute": None if router is None else router.route}
+            if retry_on is not None:
+                rkw["retry_on"] = retry_on
+        logical = batch.actor
         if router is not None:
             batch = B.MsgBatch(router.route(batch.actor), batch.a0, batch.a1, batch.a2, batch.method)
         else:
@@ -351,6 +364,8 @@ class DeviceRuntime:
             ex = self.exchange
             # more than one rank: no host wait on this Send (its overflow, if any, is
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
+            if rkw:
+                return ex.send_all(batch, logical=logical, **rkw)
             return ex.send_all(batch, defer=self.world > 1) if resend_overflow else ex.send(batch)
         from .parallel.elastic import RankFailure, is_rank_failure
 
@@ -365,7 +380,11 @@ class DeviceRuntime:
                 if dp is not None:
                     dp.begin_send()  # the host part of the Send is bounded too
                 try:
-                    out = self.exchange.send_all(sub) if resend_overflow else self.exchange.send(sub)
+                    if rkw:  # the retry rounds are part of the Send: a rank failure in one is recovered alike
+                        out = self.exchange.send_all(
+                            sub, logical=logical if todo is None else logical.index_select(0, todo), **rkw)
+                    else:
+                        out = self.exchange.send_all(sub) if resend_overflow else self.exchange.send(sub)
                 finally:
                     if dp is not None:
                         dp.end_send()
