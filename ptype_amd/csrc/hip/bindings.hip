@@ -470,6 +470,7 @@ PYBIND11_MODULE(_hip, m) {
              d["shard_ok"] = w.shard_ok;
              d["route_mode"] = w.route_mode;
              d["meta"] = std::vector<uint64_t>(w.meta, w.meta + kMetaWords);
+             d["arg_caps"] = std::vector<uint64_t>(w.arg_caps, w.arg_caps + 3);
              return d;
            },
            "geometry of the last send (region strides per peer and chunk; *_moved: words this rank sent per "
@@ -547,6 +548,7 @@ PYBIND11_MODULE(_hip, m) {
       .def_property_readonly("last_record_bytes", &Mailboxes::last_record_bytes)
       .def_property_readonly("last_view_shards", &Mailboxes::last_view_shards)
       .def_property_readonly("last_route", &Mailboxes::last_route)
+      .def_property_readonly("next_record_widths", &Mailboxes::next_record_widths)
       .def_property_readonly("consumer_processed", &Mailboxes::consumer_processed)
       .def_property_readonly("launches", &Mailboxes::launches)
       .def_property_readonly("handle", [](Mailboxes& m) { return (uintptr_t)&m; },

@@ -43,17 +43,81 @@ PackedLayout sx_layout(const uint64_t* meta) {
 
 static int sx_round_S(int S) { return S <= 4 ? S : S <= 6 ? 6 : 8; }
 
-// A field fits the layout in force (the mailbox all-ones value is reserved).
+// The reply plane is part of the layout: vb was sized from the VALUES of the lagged
+// argument maxima (packed_reply_bits: Multiply needs 2 |a| |b| < 2^(8 vb)), while a
+// request field admits by bit width, so a message can fit every field and still
+// exceed those maxima (agreed |a| <= 128: 9-bit fields hold 255, and 255 * 255 needs
+// 18 reply bits where vb = 2 holds 16).  The sender therefore admits Multiply
+// arguments by VALUE: zz(a0) <= arg[0] and zz(a1) <= arg[1], caps derived from the
+// layout and the agreement in force alone (every rank derives the same ones) --
+// starting from the agreed maxima (which fit by construction when that agreement saw
+// Multiply), a0's cap is raised as far as its field and the bound allow, then a1's.
+// A message past them is answered STATUS_OVERFLOW like one past a field (its maxima
+// enter this Send's agreement, so the re-send two Sends on fits), and no receiver
+// meets a reply wider than the plane.  Echo and PrimeCheck replies are bounded by the
+// field widths only while the agreement in force flagged the method (vb is sized
+// from the flagged methods alone), so they are capped by the plane itself: Echo's a0
+// by its all-ones (the reply is a0), PrimeCheck's arguments by one less (its bound is
+// max z + 1) -- no-ops under an agreement that saw the method, a refusal (and a
+// re-send under a layout that did) under one that did not.  State-dependent replies
+// have no bound the sender can evaluate (theirs stays the receiver's check).  A
+// uniform batch's caps are chosen here for its method: a compare per argument, where
+// the field test was a shift and a compare; a batch with a method column takes
+// Multiply's from arg[] and derives the others per message from `pure`.
+static void sx_arg_caps(const PackedLayout& L, const uint64_t* meta, bool agreed, bool mcol, uint32_t method,
+                        SxCaps& caps) {
+  const uint64_t f0 = low_mask(L.w[2]), f1 = low_mask(L.w[3]), f2 = low_mask(L.w[4]);
+  caps.arg[0] = f0, caps.arg[1] = f1, caps.arg[2] = f2;
+  caps.pure = L.vb >= 8 ? ~0ull : low_mask(8 * L.vb);
+  if (L.vb >= 8) return;
+  if (!mcol && method == kEcho) caps.arg[0] = std::min(f0, caps.pure);
+  if (!mcol && method == kPrimeCheck) {
+    caps.arg[0] = std::min(f0, caps.pure - 1), caps.arg[1] = std::min(f1, caps.pure - 1);
+    caps.arg[2] = std::min(f2, caps.pure - 1);
+  }
+  if (!mcol && method != kCalculatorMultiply) return;
+  using u128 = unsigned __int128;
+  const u128 lim = (u128)1 << (8 * L.vb);
+  auto mag = [](uint64_t z) { return (u128)(z / 2 + (z & 1)); };  // |v| <= mag(zz(v))
+  auto ok = [&](uint64_t x, uint64_t y) { return 2 * mag(x) * mag(y) < lim; };
+  // the largest x <= f with ok(x, y): mag(x) <= (lim - 1) / (2 mag(y)), and mag(2 q) = q
+  auto widest = [&](uint64_t f, uint64_t y) {
+    if (ok(f, y)) return f;
+    const u128 q = (lim - 1) / (2 * mag(y));
+    return (uint64_t)std::min<u128>(f, 2 * q);
+  };
+  uint64_t a0 = 0, a1 = 0;
+  if (agreed && meta[kMetaFlags + kCalculatorMultiply]) {
+    a0 = std::min(meta[kMetaArg0], f0), a1 = std::min(meta[kMetaArg0 + 1], f1);
+    if (!ok(a0, a1)) a0 = a1 = 0;  // (cannot happen: vb was sized from these maxima)
+  }
+  a0 = std::max(a0, widest(f0, a1));
+  a1 = std::max(a1, widest(f1, a0));
+  caps.arg[0] = a0, caps.arg[1] = a1;
+}
+
+// A message fits the layout in force (the mailbox all-ones value is reserved; the
+// arguments by the caps above).
 // reject_ordered: the agreement in force saw no ordered method, so no rank
 // sorts by actor shard this Send and the receivers skip their ordered drain --
 // an ordered message overflows (re-sent once the agreement carries its method).
-__device__ __forceinline__ bool sx_fits(const PackedLayout& L, uint32_t meth, uint32_t hdr_method, uint32_t mb,
-                                        uint64_t z0, uint64_t z1, uint64_t z2, bool reject_ordered) {
+__device__ __forceinline__ bool sx_fits(const PackedLayout& L, const SxCaps& caps, bool mcol, uint32_t meth,
+                                        uint32_t hdr_method, uint32_t mb, uint64_t z0, uint64_t z1, uint64_t z2,
+                                        bool reject_ordered) {
   auto fits = [&](int q, uint64_t v) { return L.w[q] >= 64 || (v >> L.w[q]) == 0; };
   if (reject_ordered && method_ordered(meth)) return false;
   if (L.w[0] ? !fits(0, meth) : meth != hdr_method) return false;
   if (L.w[1] == 0 || (uint64_t)mb >= low_mask(L.w[1])) return false;
-  return fits(2, z0) && fits(3, z1) && fits(4, z2);
+  uint64_t c0 = caps.arg[0], c1 = caps.arg[1], c2 = caps.arg[2];
+  if (mcol && meth != kCalculatorMultiply) {  // (arg[0..1]: Multiply's; arg[2]: the field)
+    const bool prime = meth == kPrimeCheck;
+    const uint64_t lim = meth == kEcho ? caps.pure : prime ? caps.pure - (caps.pure != ~0ull) : ~0ull;
+    const uint64_t f0 = low_mask(L.w[2]), f1 = low_mask(L.w[3]);
+    c0 = f0 < lim ? f0 : lim;
+    c1 = prime && lim < f1 ? lim : f1;
+    c2 = prime && lim < c2 ? lim : c2;
+  }
+  return z0 <= c0 && z1 <= c1 && z2 <= c2;
 }
 
 // A received region sorted by actor shard (its sender's batch may carry ordered
@@ -333,7 +397,7 @@ __global__ __launch_bounds__(kST) void sx_scatter_kernel(SortIn in, int R, uint3
         acc.flags |= 1u << (meth < 7 ? meth : 7);
       }
       uint64_t f[5];
-      const bool fit = sx_fits(L, meth, in.method_uniform, mb[k], z0, z1, z2, reject_ordered);
+      const bool fit = sx_fits(L, caps, in.mcol != nullptr, meth, in.method_uniform, mb[k], z0, z1, z2, reject_ordered);
       if (fit) {
         f[0] = meth, f[1] = mb[k], f[2] = z0, f[3] = z1, f[4] = z2;
         perm[i] = (int32_t)(rk * C + pos);
@@ -550,7 +614,7 @@ __device__ __forceinline__ void sx_onesweep_body(SortIn in, int R, unsigned long
       acc.flags |= 1u << (meth < 7 ? meth : 7);
     }
     uint64_t f[5];
-    const bool fit = sx_fits(L, meth, in.method_uniform, mb[k], z0, z1, z2, reject_ordered);
+    const bool fit = sx_fits(L, caps, in.mcol != nullptr, meth, in.method_uniform, mb[k], z0, z1, z2, reject_ordered);
     if (fit) {
       f[0] = meth, f[1] = mb[k], f[2] = z0, f[3] = z1, f[4] = z2;
       perm[i] = (int32_t)(rk * C + pos);
@@ -1202,6 +1266,7 @@ void SortedExchange::send(const SxSend& a) {
   // rank sent to q, so the inbound capacities are the outbound ones.
   const bool loop = fake_ && fake_->loopback();
   SxCaps caps_out{}, caps_in{};
+  sx_arg_caps(L, spec_meta_, agreed_, a.method_col != 0, (uint32_t)a.method_uniform, caps_out);
   size_t rq_send[kSxMaxRanks], rq_recv[kSxMaxRanks], rp_send[kSxMaxRanks], rp_recv[kSxMaxRanks];
   int64_t req_moved = 0, rep_moved = 0;
   for (int q = 0; q < R_; ++q) {
@@ -1228,6 +1293,7 @@ void SortedExchange::send(const SxSend& a) {
   wire_.rep_moved = rep_moved;
   wire_.pairs = pairs;
   std::copy(caps_out.c, caps_out.c + kSxMaxRanks, wire_.cap_out);
+  std::copy(caps_out.arg, caps_out.arg + 3, wire_.arg_caps);
   std::copy(caps_in.c, caps_in.c + kSxMaxRanks, wire_.cap_in);
   const int cur = (int)(sends_ & 1);
   uint64_t* meta = meta_dev_ + cur * kSxMetaWords;

@@ -67,6 +67,10 @@ constexpr int kSxMetaPair = kMetaWords;
 constexpr int kSxMetaWords = kMetaWords + kSxMaxRanks * kSxMaxRanks;
 struct SxCaps {  // per-destination capacities (records), by value into the sender's kernels
   uint32_t c[kSxMaxRanks];
+  // sender admission (exchange_sorted.hip sx_arg_caps): zz(a_j) <= arg[j]; pure: the widest
+  // zigzag reply the plane holds (a method column's Echo / PrimeCheck messages)
+  uint64_t arg[3];
+  uint64_t pure;
 };
 
 struct SxSend {
@@ -101,6 +105,7 @@ struct SxWire {
   int route_mode = 0;       // sender resolution: 0 hash, 1 directory, 2 affine, 3 rank byte table
   int64_t spec_from = -1;   // the Send whose agreement they came from
   uint64_t meta[kMetaWords] = {};
+  uint64_t arg_caps[3] = {};  // the sender's admission caps on zz(a0..a2) (SxCaps::arg)
 };
 
 class SortedExchange {

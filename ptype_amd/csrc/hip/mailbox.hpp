@@ -215,6 +215,10 @@ class Mailboxes {
   uint32_t last_view_shards() const { return last_view_shards_; }
   // the last sorted Send's route: 0 hash probe, 1 directory, 2 affine rule, 3 rank byte table
   int last_route() const { return last_route_; }
+  // the 8-B field widths the next 8-B Send will run on, as the device left them in the
+  // pinned mirror: wm | w0 << 8 | w1 << 16, bit 31 = the fields outgrew 8 B.  -1 before
+  // the first 8-B Send; current once the stream of the last Send is synchronised.
+  int64_t next_record_widths() const { return r8host_ ? (int64_t)__atomic_load_n(r8host_, __ATOMIC_RELAXED) : -1; }
   uint64_t consumer_processed() const;
   uint64_t launches() const { return launches_; }
   const MboxView& view() const { return mv_; }

@@ -78,6 +78,17 @@ class Mailboxes:
         return int(self._m.last_route)
 
     @property
+    def next_record_widths(self):
+        """``(wm, w0, w1, wide)``: the 8-B record field widths (mailbox or actor id, zigzag
+        a0, zigzag a1) the next 8-B Send runs on, as the last one's kernels derived them;
+        ``wide``: the fields outgrew 52 bits, so the next Send leaves 8-B records.  ``None``
+        before the first 8-B Send.  Read it after synchronising the Send's stream."""
+        w = int(self._m.next_record_widths)
+        if w < 0:
+            return None
+        return w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff, bool(w >> 31)
+
+    @property
     def handle(self) -> int:
         """Address of the native object: the epoch engine delivers received records into it."""
         return int(self._m.handle)

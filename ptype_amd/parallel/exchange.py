@@ -45,6 +45,7 @@ from __future__ import annotations
 import collections
 import math
 import threading
+import weakref
 from dataclasses import dataclass
 
 import torch
@@ -1022,11 +1023,16 @@ class _FakeAgree:
 
     @classmethod
     def of(cls, fc) -> "_FakeAgree":
+        # keyed by id(fc) but bound to the object: a FakeComm created after another one
+        # was freed can get its address, and must not inherit that one's agreement (its
+        # rank count, a barrier a failed rank left broken)
         with cls._lock:
-            a = cls._by_comm.get(id(fc))
-            if a is None:
-                a = cls._by_comm[id(fc)] = cls(int(fc.size))
-            return a
+            ent = cls._by_comm.get(id(fc))
+            if ent is None or ent[0]() is not fc:
+                for k in [k for k, e in cls._by_comm.items() if e[0]() is None]:
+                    del cls._by_comm[k]  # (freed communicators' entries)
+                ent = cls._by_comm[id(fc)] = (weakref.ref(fc), cls(int(fc.size)))
+            return ent[1]
 
     def max(self, rank: int, v: int) -> int:
         self.vals[rank] = v

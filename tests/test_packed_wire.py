@@ -242,6 +242,19 @@ def test_gpu_packed_exchange_simulated_ranks(R, mcol, big, direct):
     C = B.stripe_capacity(M, R)
     tabs = [_tables(n, R, True) for _ in range(R)]
     cbs = [_mixed_batch(M - 1000 * r, n, 100 + r, mcol=mcol and r != 1, big=big) for r in range(R)]  # rank 1: uniform
+    _, got, ref = _packed_vs_v2(cbs, tabs, R, n, C, direct)
+    for r in range(R):
+        assert torch.equal(got[r][1], ref[r][1]), r
+        assert torch.equal(got[r][0], ref[r][0]), r
+        assert int((got[r][1] == STATUS_NO_ACTOR).sum()) > 0
+        assert int((got[r][1] == STATUS_OK).sum()) > M // 2
+
+
+def _packed_vs_v2(cbs, tabs, R, n, C, direct=False):
+    """One exchange of the CPU batches ``cbs`` (one per rank) both ways: wire v3 on the
+    GPU under the layout agreed from the GPU width pass (checked against the reference
+    width pass), and the v2 CPU reference pipeline.  Returns (layout, v3 results, v2
+    results), results per rank as (value, status) on the CPU."""
     metas = []
     for r in range(R):
         _, n_dir, aw = tabs[r][0].directory()
@@ -252,11 +265,7 @@ def test_gpu_packed_exchange_simulated_ranks(R, mcol, big, direct):
     cst = [torch.zeros(n // R + 1, dtype=torch.int64) for _ in range(R)]
     got = _simulate([_cuda(b) for b in cbs], [t[0] for t in tabs], gst, R, C, L, packed=True, direct=direct)
     ref = _simulate(cbs, [t[1] for t in tabs], cst, R, C, L, packed=False, direct=direct)
-    for r in range(R):
-        assert torch.equal(got[r][1], ref[r][1]), r
-        assert torch.equal(got[r][0], ref[r][0]), r
-        assert int((got[r][1] == STATUS_NO_ACTOR).sum()) > 0
-        assert int((got[r][1] == STATUS_OK).sum()) > M // 2
+    return L, got, ref
 
 
 _ENGINE_SCRIPT = textwrap.dedent("""

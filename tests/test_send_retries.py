@@ -182,6 +182,29 @@ def test_send_all_retries_refuses_ordered_and_bad_arguments():
         ex.send_all(MsgBatch(ids, a0, None, None, METHOD_RETRY_TEST), retries=1)
 
 
+def test_fake_agreement_is_bound_to_its_communicator():
+    """The in-process ranks' agreement is looked up by the communicator's address: a
+    FakeComm created after another one was freed can get that address and must get an
+    agreement of its own size (a 4-rank comm once inherited a freed 2-rank comm's and
+    its ranks 2 and 3 failed with an IndexError, the others at the barrier)."""
+    from ptype_amd.parallel.exchange import _FakeAgree
+
+    class Comm:
+        def __init__(self, size):
+            self.size = size
+
+    old = Comm(2)
+    a = _FakeAgree.of(old)
+    assert a.R == 2 and _FakeAgree.of(old) is a
+    key = id(old)
+    del old  # freed: a new communicator at the same address (moved there by hand: deterministic)
+    new = Comm(4)
+    _FakeAgree._by_comm[id(new)] = _FakeAgree._by_comm.pop(key)
+    b = _FakeAgree.of(new)
+    assert b is not a and b.R == 4 and len(b.vals) == 4
+    assert _FakeAgree.of(new) is b
+
+
 def test_runtime_send_retries_cpu():
     from ptype_amd.runtime import DeviceRuntime
 
