@@ -219,7 +219,16 @@ class Client:
         Opt-in (``retries=client.cfg.retries`` for the reference's behaviour): it
         costs a host read per Send, and a retried message runs after the rest of
         its batch, so a batch with an ordered method is refused.  ``None``: one
-        attempt, exactly the Send above."""
+        attempt, exactly the Send above.
+
+        ``account=`` (keyword, forwarded to ``DeviceRuntime.send``): whether the
+        Send ledger (``gpu.ledger: true``; ``Stats()["runtime"]["ledger"]``)
+        accounts this Send -- per-method call counts, a digest of every reply, an
+        audit of the pure methods and per-actor load, folded in on the device once
+        the replies are final.  ``None`` follows the runtime's setting, ``False``
+        skips this Send, ``True`` without a ledger raises.  An accounted Send does
+        not defer its overflow re-sends, and the ledger is the caller's view: each
+        rank accounts the batches it sent."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:

@@ -330,6 +330,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("cpu", &GpuConfig::cpu)
       .def_readwrite("mailbox_shards", &GpuConfig::mailbox_shards)
       .def_readwrite("mailbox_slots", &GpuConfig::mailbox_slots)
+      .def_readwrite("ledger", &GpuConfig::ledger)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

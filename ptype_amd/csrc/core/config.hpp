@@ -62,6 +62,7 @@ struct GpuConfig {
   // "ipc" (IpcComm: shared-memory segments every rank maps, over a gloo group; ranks may share a GPU)
   std::string comm = "rccl";
   bool watch = true;          // follow the store (shard records, leases) into the GPU registry mirror
+  bool ledger = false;        // Send ledger in HBM (ops/ledger.py): per-method counts, reply digest, audit
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

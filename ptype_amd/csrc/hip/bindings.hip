@@ -12,6 +12,7 @@
 #include "engine.hpp"
 #include "exchange_sorted.hpp"
 #include "ipc_comm.hpp"
+#include "ledger.hpp"
 #include "mailbox.hpp"
 #include "server.hpp"
 #include "xcall.hpp"
@@ -84,6 +85,9 @@ int64_t retry_tile();
 void launch_retry_select(uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                          uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
 void launch_retry_merge(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
+int64_t ledger_tile();
+void launch_ledger_account(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t,
+                           uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -264,6 +268,31 @@ PYBIND11_MODULE(_hip, m) {
         "every non-null column, K in k_out[0]; counts: ceil(M / retry_tile()) u32 words of workspace");
   m.def("retry_merge", &launch_retry_merge, py::arg("val"), py::arg("st"), py::arg("M"), py::arg("idx"), py::arg("v2"),
         py::arg("s2"), py::arg("K"), py::arg("stream"), "val[idx[j]] = v2[j], st[idx[j]] = s2[j] for j < K");
+
+  // ---- Send ledger (ledger.hip, ledger.hpp): a Send's final replies folded into counters in HBM
+  m.def("ledger_tile", &ledger_tile, "messages per block of ledger_account");
+  m.def("ledger_words", []() {
+    py::dict d;
+    d["calls"] = kLedgerCalls;
+    d["method_slots"] = kLedgerMethodSlots;
+    d["status_slots"] = kLedgerStatusSlots;
+    d["messages"] = kLedgerMessages;
+    d["sends"] = kLedgerSends;
+    d["digest_sum"] = kLedgerDigestSum;
+    d["digest_xor"] = kLedgerDigestXor;
+    d["audited"] = kLedgerAudited;
+    d["mismatch"] = kLedgerMismatch;
+    d["load_oob"] = kLedgerLoadOob;
+    d["words"] = kLedgerWords;
+    d["copies"] = kLedgerCopies;
+    d["ticket_words"] = (int)kTicketWords;
+    return d;
+  }, "word indices of the ledger block (ledger.hpp) and the sizes of its buffers");
+  m.def("ledger_account", &launch_ledger_account, py::arg("status"), py::arg("value"), py::arg("M"), py::arg("actor"),
+        py::arg("method_col"), py::arg("method_uniform"), py::arg("a0"), py::arg("a1"), py::arg("ledger"),
+        py::arg("load"), py::arg("n_load"), py::arg("ticket"), py::arg("stream"),
+        "one pass over a Send's replies and batch columns into ledger (copies x words of ledger_words() int64), the optional "
+        "per-actor load table (n_load int64) and sends; ticket: ledger_words()['ticket_words'] zeroed u32");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

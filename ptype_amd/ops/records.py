@@ -38,6 +38,17 @@ STATUS_OVERFLOW = 4
 STATUS_NOT_DELIVERED = 5
 STATUS_RANK_LOST = 6  # the actor's rank died with the message in flight (re-homed since: re-send)
 
+# names for people (Stats(), the Send ledger): the net/rpc service methods the ids stand for
+METHOD_NAMES = {
+    METHOD_NONE: "none", METHOD_CALC_MULTIPLY: "Calculator.Multiply", METHOD_PRIME_CHECK: "Prime.Check",
+    METHOD_ECHO: "Echo", METHOD_RETRY_TEST: "RPCRetryTest.Call", METHOD_COUNTER_ADD: "Counter.Add",
+    METHOD_FORWARD: "Forward", METHOD_SEQ_FOLD: "SeqFold", METHOD_RELAY: "Relay", METHOD_COORD_PRIME: "Coordinator.Prime",
+}
+STATUS_NAMES = {
+    STATUS_OK: "ok", STATUS_NO_METHOD: "no_method", STATUS_FAILED: "failed", STATUS_NO_ACTOR: "no_actor",
+    STATUS_OVERFLOW: "overflow", STATUS_NOT_DELIVERED: "not_delivered", STATUS_RANK_LOST: "rank_lost",
+}
+
 MSG_WORDS = 4    # int64 words per 32-B message record
 REPLY_WORDS = 2  # int64 words per 16-B reply record
 

@@ -426,11 +426,20 @@ class ActorExchange:
             return None
         return dist.all_to_all_single(out, inp, group=self.group, async_op=True)
 
-    def send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None):
+    def send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None,
+             ledger=None):
         """Deliver every message of ``req`` (a SoA ``MsgBatch``) to its actor and return
         ``(value int64[M], status int32[M])`` in message order.  Collective:
         every rank of the group must call it (with its own, possibly empty, batch)
-        the same number of times."""
+        the same number of times.  ``ledger``: an ``ops.ledger.Ledger`` that accounts
+        this Send's replies -- one more kernel on the Send's own stream (no stream
+        fork, no host read; capturable)."""
+        val, st = self._send(req, out_val, out_status)
+        if ledger is not None:
+            ledger.account(req, val, st)
+        return val, st
+
+    def _send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None):
         if self._deferred and not self._capturing:  # a deferred Send two Sends old: its agreement buffer is reused
             self._resolve_deferred(final=False)
         M = req.M
@@ -526,7 +535,7 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def capture(self, req: B.MsgBatch, out_val: torch.Tensor, out_status: torch.Tensor, prologue=None,
-                allow_collectives: bool = False, repeat: int = 1) -> "SendGraph":
+                allow_collectives: bool = False, repeat: int = 1, ledger=None) -> "SendGraph":
         """Capture ``send(req)`` (plus an optional ``prologue()``, e.g. a kernel
         that refills ``req``) into a hipGraph for fixed-shape steady-state epochs:
         one graph launch replaces the ~6 kernel launches + host logic per chunk,
@@ -534,10 +543,11 @@ class ActorExchange:
         Send) rounds in one graph -- one replay per ``repeat`` steps, for batches
         small enough that the graph launch itself shows; ``prologue(j)`` then gets
         the step's index j within the replay.  Single rank by default;
-        RCCL collectives are capturable but opt-in (``allow_collectives``)."""
+        RCCL collectives are capturable but opt-in (``allow_collectives``).
+        ``ledger``: every captured step is accounted (see ``SendGraph``)."""
         if (self.world > 1 or self.force_collectives) and not allow_collectives:
             raise RuntimeError("capture: collectives in a graph are opt-in (allow_collectives=True)")
-        return SendGraph(self, req, out_val, out_status, prologue, repeat)
+        return SendGraph(self, req, out_val, out_status, prologue, repeat, ledger)
 
     # ------------------------------------------------------------------
     def pump(self, outbox, initial: B.MsgBatch | None = None, max_epochs: int = 1 << 20, check_every: int = 8):
@@ -764,7 +774,7 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def send_all(self, req: B.MsgBatch, max_epochs: int = 16, out: tuple | None = None, defer: bool = False,
-                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None):
+                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None, ledger=None):
         """`send` + re-send of overflowed messages until every one is delivered.
         Reads the overflow count once per epoch (a host round trip); with adaptive
         slot capacity (native engine, wire v3) skewed traffic fits in the first
@@ -794,7 +804,20 @@ class ActorExchange:
         ``logical`` (the caller's logical actor ids, default ``req.actor``) and
         routed afresh, the reference's ``c.conns.Get()`` inside the retry closure.
         A retried message runs after the rest of its batch, so a batch that
-        carries an ordered method is refused; so is a Send under graph capture."""
+        carries an ordered method is refused; so is a Send under graph capture.
+
+        ``ledger``: an ``ops.ledger.Ledger`` that accounts this Send once, on its
+        final replies -- after the overflow re-send rounds and the retry merges, so
+        a message that was re-sent or retried is counted once, with the status it
+        ended with.  The batch is accounted under ``logical`` actor ids when given.
+        A Send with a ledger does not defer (``defer`` is treated as False, as with
+        retries): it pays the host read per re-send round that deferral avoids."""
+        if ledger is not None:
+            val, st = self.send_all(req, max_epochs, out, False, retries, retry_on, reroute, logical)
+            if logical is not None:
+                req = B.MsgBatch(logical.to(torch.int32), req.a0, req.a1, req.a2, req.method)
+            ledger.account(req, val, st)
+            return val, st
         retries = int(retries)
         if retries < 0:
             raise ValueError("retries >= 0")
@@ -1045,9 +1068,14 @@ class _FakeAgree:
 class SendGraph:
     """A captured ``ActorExchange.send`` over fixed buffers (``torch.cuda.CUDAGraph``
     is a hipGraph on ROCm).  ``replay()`` re-runs every kernel of the epoch(s) on
-    whatever ``req`` holds at that moment."""
+    whatever ``req`` holds at that moment.  ``ledger``: an ``ops.ledger.Ledger``
+    handed to the captured ``send``, so every replayed step is accounted (the
+    ledger kernel is one more node on the Send's own stream: no parallel branch).
+    The two warm-up sends before the capture are accounted too: ``reset()`` the
+    ledger after building the graph."""
 
-    def __init__(self, ex: ActorExchange, req: B.MsgBatch, out_val, out_status, prologue=None, repeat: int = 1):
+    def __init__(self, ex: ActorExchange, req: B.MsgBatch, out_val, out_status, prologue=None, repeat: int = 1,
+                 ledger=None):
         if repeat < 1:
             raise ValueError("repeat >= 1")
         self.ex, self.req, self.M, self.repeat = ex, req, req.M, int(repeat)
@@ -1059,7 +1087,7 @@ class SendGraph:
                     prologue(j)  # the step's index within the replay
                 else:
                     prologue()
-            ex.send(req, out_val, out_status)
+            ex.send(req, out_val, out_status, ledger)
 
         def body():
             for j in range(self.repeat):

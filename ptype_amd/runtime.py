@@ -71,7 +71,8 @@ class DeviceRuntime:
     def __init__(self, device=None, actors: int = 1024, ring: int = 4096, idle_ms: float = 200.0,
                  delay_us: int = 0, max_batch: int = 1 << 20, chunks: int = 0, random_state: bool = False,
                  group=None, shm: bool = True, service: str = "", mailbox_shards: int = 256,
-                 mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0):
+                 mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0,
+                 ledger: bool = False):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -129,6 +130,13 @@ class DeviceRuntime:
         # segments every rank maps, over a gloo group -- several ranks may share one GPU)
         self.comm, self.comm_timeout_s = comm or "rccl", float(comm_timeout_s)
         self._exchange = None
+        # Send ledger (ops/ledger.py, opt-in): per-method counts, a digest of every reply and
+        # per-actor load of the batches this rank sent, kept in HBM and read by stats()
+        self.ledger = None
+        if ledger:
+            from .ops.ledger import Ledger
+
+            self.ledger = Ledger(self.device, actors=self.total_actors)
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -192,7 +200,7 @@ class DeviceRuntime:
         rt = cls(device_for_rank(rank), actors=g.actors, ring=g.ring, idle_ms=g.idle_ms, delay_us=g.delay_us,
                  max_batch=g.max_batch, service=cfg.service_name, mailbox_shards=g.mailbox_shards,
                  mailbox_slots=g.mailbox_slots, delivery=g.delivery, comm=g.comm,
-                 comm_timeout_s=g.group_timeout_s, group=native)
+                 comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -336,7 +344,7 @@ class DeviceRuntime:
         return ReplicaRouter(service, self.world0, la, max_connections, kv=self._kv)
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
-             retries: int | None = None, retry_on=None):
+             retries: int | None = None, retry_on=None, account: bool | None = None):
         """Batched Send: every message to its actor anywhere in the node and the
         replies back in message order.  Collective across the process group.
         Registry changes seen since the last Send are applied first.  With an
@@ -346,7 +354,16 @@ class DeviceRuntime:
         ``retries``: up to that many further attempts of every message whose status
         is in ``retry_on`` (default STATUS_FAILED), each through ``router`` again --
         the reference's ``withRetry`` (``ActorExchange.send_all``).  None or 0: one
-        attempt, no retry work at all."""
+        attempt, no retry work at all.
+        ``account``: whether the Send ledger (``DeviceRuntime(ledger=True)``,
+        ``gpu.ledger``) accounts this Send -- once, on its final replies, under the
+        batch's logical actor ids.  None follows the runtime's setting, False skips
+        this Send, True without a ledger raises.  An accounted Send does not defer
+        its overflow re-sends."""
+        if account and self.ledger is None:
+            raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
+                             "gpu.ledger)")
+        ledger = self.ledger if account is None or account else None
         rkw = {}
         if retries:
             if not resend_overflow:
@@ -362,6 +379,12 @@ class DeviceRuntime:
         self.sync()
         if self.membership is None:
             ex = self.exchange
+            if ledger is not None:  # accounted on its final replies: never deferred
+                if resend_overflow:
+                    return ex.send_all(batch, logical=logical, ledger=ledger, **rkw)
+                out = ex.send(batch)
+                ledger.account(self._logical_batch(batch, logical), out[0], out[1])
+                return out
             # more than one rank: no host wait on this Send (its overflow, if any, is
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
             if rkw:
@@ -422,13 +445,25 @@ class DeviceRuntime:
                         raise
                     self.recover()  # the batch WAS delivered: recover, never re-send it
             if todo is None:
+                if ledger is not None:
+                    ledger.account(self._logical_batch(batch, logical), out[0], out[1])
                 return out
             val = torch.zeros(batch.M, dtype=out[0].dtype, device=out[0].device)
             st = torch.full((batch.M,), STATUS_RANK_LOST, dtype=out[1].dtype, device=out[1].device)
             val[todo] = out[0]
             st[todo] = out[1]
+            if ledger is not None:  # the whole batch, the STATUS_RANK_LOST rows included
+                ledger.account(self._logical_batch(batch, logical), val, st)
             return (val, st) + tuple(out[2:])
         raise AssertionError("unreachable")
+
+    @staticmethod
+    def _logical_batch(batch: B.MsgBatch, logical: torch.Tensor) -> B.MsgBatch:
+        """``batch`` as its caller addressed it (a replica router rewrote the actor
+        column): what the Send ledger accounts."""
+        if logical is batch.actor:
+            return batch
+        return B.MsgBatch(logical.to(torch.int32), batch.a0, batch.a1, batch.a2, batch.method)
 
     def _failed(self) -> str:
         """Why the current generation was failed ("" while fine)."""
@@ -742,6 +777,8 @@ class DeviceRuntime:
             out["mirror"] = {"applies": self.mirror.applies, "actors": self.mirror.actors}
         if self._exchange is not None:
             out["exchange"] = asdict(self._exchange.stats())
+        if self.ledger is not None:
+            out["ledger"] = self.ledger.read()
         return out
 
     def close(self) -> None:
