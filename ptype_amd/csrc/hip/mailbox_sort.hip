@@ -68,10 +68,39 @@ static bool fused_ok(int64_t tiles) {
   return f == 1 || (f < 0 && tiles <= 512);
 }
 
+// The persistent presence-map sort (tune mbox_persist): auto takes it for batches past 512
+// tiles, where every resident block has more than one tile to walk.
+static bool persist_ok(int64_t tiles) {
+  const int p = tune().mbox_persist;
+  return p == 1 || (p < 0 && tiles > 512);
+}
+
+// Its grid: the blocks the device keeps resident at this LDS size, at most one per tile,
+// a multiple of 8 from 8 up (whole XCD rounds).  (The current device is the Send's.)
+static uint32_t persist_grid(size_t lds, int64_t tiles) {
+  thread_local int c_dev = -1, c_resident = 0;  // the last answer (a Send repeats its device and map size)
+  thread_local size_t c_lds = 0;
+  int dev = 0;
+  PT_HIP_CHECK(hipGetDevice(&dev));
+  if (dev != c_dev || lds != c_lds) {
+    int cus = 0, per_cu = 0;
+    PT_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    PT_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)mbx_persist_sort_kernel<>, kST, lds));
+    c_resident = std::max(per_cu, 1) * std::max(cus, 1);
+    c_dev = dev, c_lds = lds;
+  }
+  int64_t g = std::min<int64_t>(c_resident, tiles);
+  if (g >= 8) g -= g % 8;
+  return (uint32_t)g;
+}
+
 // Removed variants (measured slower or flat; A/B rows in profiles/r4_mailbox_ab.md and
 // profiles/r5_mailbox_ab.md): the look-back sort for stateless batches (run reservations
-// won), the persistent reserving sort (42.8 vs 50.5 G msg/s), 1024- and 2048-message tiles
-// for the fused / separate sort, arguments loaded after the look-back, the LDS-table count,
+// won), the persistent reserving sort with ONE block per CU that prefetched whole tiles (42.8
+// vs 50.5 G msg/s; the kept one, mbx_persist_sort_kernel, runs two per CU and carries only the
+// next tile's actors and ranks), the tile's store loop as one shared function (5-15 VGPRs more
+// in every sort kernel; profiles/persistent_sort.md), 1024- and 2048-message tiles for the
+// fused / separate sort, arguments loaded after the look-back, the LDS-table count,
 // the group look-back, non-temporal directory gathers and reply stores, the binned ordered
 // drain (233 vs 175 us), 2048-record ordered windows, the ordered drain without the
 // register fold or the prefetched window, 16-B ordered records at 8 Mi, the wide ring
@@ -424,12 +453,19 @@ void Mailboxes::send_sorted(const MboxSend& a) {
     }
     const size_t os_lds = pres_route ? ((onesweep_lds_bytes(Sv) + 15) & ~(size_t)15) + (size_t)pres_words(a.n_dir) * 4
                                      : onesweep_lds_bytes(Sv);
+    // the persistent form of the presence-map sort (mbx_persist_sort_kernel): resident blocks walk the tiles
+    const bool persist = pres_route && persist_ok(tiles);
     if (pres_route) {
       static bool attr = false;
       if (!attr) {  // (past the 64 KB default for the largest maps)
         PT_HIP_CHECK(hipFuncSetAttribute((const void*)mbx_onesweep_kernel<4, false, false>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)(((onesweep_lds_bytes(kMboxSortMaxShards) + 15) & ~(size_t)15) +
+                                               (size_t)pres_words(kPresMax) * 4)));
+        // (the persistent form serves stateless views only: at most kStatelessShards shards)
+        PT_HIP_CHECK(hipFuncSetAttribute((const void*)mbx_persist_sort_kernel<>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(((persist_lds_bytes(kStatelessShards) + 15) & ~(size_t)15) +
                                                (size_t)pres_words(kPresMax) * 4)));
         attr = true;
       }
@@ -446,7 +482,11 @@ void Mailboxes::send_sorted(const MboxSend& a) {
     else if (a.method_col) PT_OS1(MO, false, true); \
     else PT_OS1(MO, false, false);                  \
   } while (0)
-    if (pres_route) PT_OS1(4, false, false);
+    if (persist) {
+      const size_t ps_lds = ((persist_lds_bytes(Sv) + 15) & ~(size_t)15) + (size_t)pres_words(a.n_dir) * 4;
+      hipLaunchKernelGGL(mbx_persist_sort_kernel<>, dim3(persist_grid(ps_lds, tiles)), dim3(kST), ps_lds, st, in, mv,
+                         sort_sidx_, tinfo, sort_rw_, rv);
+    } else if (pres_route) PT_OS1(4, false, false);
     else if (rank_route) PT_OS1(3, false, false);
     else if (mode == 2) PT_OS(2); else if (mode == 1) PT_OS(1); else PT_OS(0);
 #undef PT_OS

@@ -365,6 +365,173 @@ __device__ __forceinline__ void resolve_pres(const SortIn& in, const uint32_t* l
   }
 }
 
+// ---- the phases of a one-pass tile, shared by onesweep_tile (one tile per block) and the
+// persistent reserving sort (mbx_persist_sort_kernel: a block walks several tiles)
+//
+// Phase 1: the tile's actors resolved to (rank, mailbox).
+template <int MODE, int SK>
+__device__ __forceinline__ void os_resolve(const SortIn& in, const uint32_t* lpres, const uint32_t (&a)[SK], int (&r)[SK],
+                                           uint32_t (&mb)[SK]) {
+  if constexpr (MODE == 4) resolve_pres<SK>(in, lpres, a, r, mb);
+  else resolve_k<MODE, SK>(in, a, r, mb);
+}
+
+// Phase 2: each message's rank among its wave's earlier messages of its shard (message
+// order: item, then lane), counted into this wave's row `wrow` of the wave counts.  A
+// message past the batch, of another rank or without an actor leaves with mb = kNoSlot.
+template <int SK>
+__device__ __forceinline__ void os_rank(const SortIn& in, uint32_t log_s, uint32_t t, const int (&r)[SK],
+                                        uint32_t (&mb)[SK], uint32_t* wrow, uint32_t (&wr)[SK]) {
+  const uint32_t S = 1u << log_s;
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const bool ok = tile_index<SK>(t, k) < in.M && r[k] == in.rank_self && mb[k] < kMaxMbox;
+    if (!ok) mb[k] = kNoSlot;
+    const uint32_t sh = mb[k] & (S - 1);
+    const uint64_t peers = match_bits(sh, log_s, __ballot(ok));
+    const unsigned below = mbcnt64(peers);
+    const int leader = peers ? __builtin_ctzll(peers) : 0;
+    unsigned old = 0;
+    if (ok && below == 0) {
+      old = wrow[sh];
+      wrow[sh] = old + (unsigned)__popcll(peers);
+    }
+    wr[k] = (unsigned)__shfl((int)old, leader) + below;
+  }
+}
+
+// Phase 3, per shard (one thread each): the wave counts turned into wave offsets (returns
+// the tile's count), the run's reservation, the ring's room, and the run's tinfo words.
+__device__ __forceinline__ uint32_t os_wave_offsets(uint32_t* wcnt_all, uint32_t S, uint32_t s) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int ww = 0; ww < kST / kWave; ++ww) {
+    const uint32_t x = wcnt_all[ww * S + s];
+    wcnt_all[ww * S + s] = c;
+    c += x;
+  }
+  return c;
+}
+__device__ __forceinline__ uint32_t os_reserve(const MboxView& mv, uint32_t s, uint32_t c) {
+  return c ? atomicAdd(&mv.resv[s * kResvStride], c) : 0u;
+}
+__device__ __forceinline__ uint32_t os_ring_room(const MboxView& mv, uint32_t s, uint64_t& tl) {
+  const uint64_t Q = 1ull << mv.log_q;
+  tl = *ctr_tail(mv, s);
+  const uint64_t hd = *ctr_head(mv, s);
+  const uint64_t free = hd + Q > tl ? hd + Q - tl : 0;
+  return (uint32_t)(free < 0xffffffffull ? free : 0xffffffffull);
+}
+// (returns whether the run overran the ring's room)
+__device__ __forceinline__ int os_run_info(const MboxView& mv, uint32_t* __restrict__ tinfo, uint32_t t, uint32_t S,
+                                           uint32_t s, uint64_t tl, uint32_t rm, uint64_t excl, uint32_t c) {
+  if (tinfo) {
+    const uint32_t cc = excl >= rm ? 0u : (uint32_t)min((uint64_t)c, rm - excl);
+    tinfo[(size_t)t * 2 * S + s] = (uint32_t)(tl + excl) + shard_rot(mv, s);
+    tinfo[(size_t)t * 2 * S + S + s] = cc | (excl + c > rm ? kRunSpilled : 0u);
+  }
+  return excl + c > rm;
+}
+
+// (in.rec8 / in.recw) the tile's fields OR-ed, their bit lengths max-ed into `tmax` (LDS,
+// read past the next barrier); returns the mask of this thread's messages whose fields do
+// not fit an 8-B record of widths `w8`.
+template <int SK>
+__device__ __forceinline__ uint32_t os_fields(const SortIn& in, uint32_t w8, const uint32_t (&mb)[SK],
+                                              const int64_t (&v0)[SK], const int64_t (&v1)[SK], uint32_t* tmax) {
+  uint32_t escm = 0;
+  if (!(in.rec8 || in.recw)) return escm;
+  uint64_t or_m = 0, or_0 = 0, or_1 = 0;
+  const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu, w1 = (w8 >> 16) & 0xffu;
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    if (mb[k] == kNoSlot) continue;
+    const uint64_t z0 = ((uint64_t)v0[k] << 1) ^ (uint64_t)(v0[k] >> 63);
+    const uint64_t z1 = ((uint64_t)v1[k] << 1) ^ (uint64_t)(v1[k] >> 63);
+    or_m |= mb[k], or_0 |= z0, or_1 |= z1;
+    if (in.rec8 && ((mb[k] >> wm) != 0 || (z0 >> w0) != 0 || (z1 >> w1) != 0)) escm |= 1u << k;
+  }
+  const uint32_t bm = wave_max_u32(bitlen64(or_m)), b0 = wave_max_u32(bitlen64(or_0)),
+                 b1 = wave_max_u32(bitlen64(or_1));
+  if (lane_id() == 0) {
+    atomicMax(&tmax[0], bm);
+    atomicMax(&tmax[1], b0);
+    atomicMax(&tmax[2], b1);
+  }
+  return escm;
+}
+
+// A tile's ranks (below kST), two to a word: what the persistent sort carries to the store phase.
+template <int SK>
+struct PackedRanks {
+  uint32_t p[SK / 2];
+  __device__ __forceinline__ uint32_t operator[](int k) const { return (p[k >> 1] >> ((k & 1) * 16)) & 0xffffu; }
+};
+
+// Phase 4, per message i of the tile (the caller's unrolled loop over its items: the loop
+// inside a shared function cost every sort kernel 5 to 15 VGPRs): the record into its ring
+// at the run's prefix + the wave's offset + the message's rank; a message past the ring's
+// room (or, stateless, one whose fields do not fit 8 B) spills or overflows.  `wrow` is this
+// wave's row of the wave offsets.
+template <int SK, typename CT>
+__device__ __forceinline__ void os_store_msg(const SortIn& in, const MboxView& mv, const ReplyView& rv, int64_t i,
+                                             const unsigned long long* base, const uint32_t* room, const uint32_t* pre,
+                                             const uint32_t* wrow, uint32_t mbk, uint32_t wrk, int64_t x0, int64_t x1,
+                                             int64_t x2, uint32_t mt, bool esc, uint32_t w8, bool spill, bool wsidx,
+                                             uint32_t* __restrict__ sidx, uint32_t* __restrict__ rw, CT& n_enq, CT& n_ovf,
+                                             CT& n_miss, CT& n_spill) {
+  const uint32_t S = 1u << mv.log_s;
+  const uint32_t origin = in.origin_base + (uint32_t)i;
+  if (mbk == kNoSlot) {
+    ++n_miss;
+    if (wsidx) sidx[i] = kNoSlot;
+    write_status(rv, origin, kStatusNoActor);
+    return;
+  }
+  const uint32_t sh = mbk & (S - 1);
+  const uint32_t off = pre[sh] + wrow[sh] + wrk;
+  if (off >= room[sh] || (esc && spill)) {  // the ring is full (or a stateless record, esc: wider than 8 B, spills)
+    if (spill) {  // the drain runs it from the batch: its route word is all it needs from here
+      ++n_spill;
+      sidx[i] = kSpillSlot;
+      rw[i] = mbk;
+      return;
+    }
+    ++n_ovf;
+    if (wsidx) sidx[i] = kNoSlot;
+    write_status(rv, origin, kStatusOverflow);
+    return;
+  }
+  const uint64_t slot = slot_at(mv, sh, base[sh] + off);
+  if (wsidx) sidx[i] = (uint32_t)slot;
+  if (in.recw) {  // wide pure record: {a0, a1} whole, the place in the tile beside it
+    *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
+        u32x4{(uint32_t)x0, (uint32_t)((uint64_t)x0 >> 32), (uint32_t)x1, (uint32_t)((uint64_t)x1 >> 32)};
+    rec_place(mv)[slot] = (uint16_t)(i & ((kST * SK) - 1));
+  } else if (in.rec8 && esc) {  // (ordered) escape: the place in the tile + bit 63, the fields aside
+    reinterpret_cast<uint64_t*>(mv.rec)[slot] = (uint64_t)(i & ((kST * SK) - 1)) | (1ull << 63);
+    *reinterpret_cast<u32x4*>(in.r8esc + 2 * slot) =
+        u32x4{(uint32_t)x0, (uint32_t)((uint64_t)x0 >> 32), mbk, 0u};
+  } else if (in.rec8) {  // 8-B record (uniform method; stateless records that do not fit spilled above)
+    const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu;
+    const uint64_t z0 = ((uint64_t)x0 << 1) ^ (uint64_t)(x0 >> 63);
+    const uint64_t z1 = ((uint64_t)x1 << 1) ^ (uint64_t)(x1 >> 63);
+    reinterpret_cast<uint64_t*>(mv.rec)[slot] =
+        (uint64_t)(i & ((kST * SK) - 1)) | ((uint64_t)mbk << 12) | (z0 << (12 + wm)) | (z1 << (12 + wm + w0));
+  } else if (mt < 128u && fits_i32(x0) && fits_i32(x1) && x2 == 0) {
+    *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
+        u32x4{origin | kCompactMark, mbk | (mt << 24), (uint32_t)x0, (uint32_t)x1};
+  } else {
+    const uint32_t fl = x2 != 0 ? (uint32_t)kFlagA2 : 0u;
+    *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
+        u32x4{origin | kCompactMark, mbk | kCompactLong, (mt & 0xffffu) | (fl << 16), 0u};
+    *reinterpret_cast<u32x4*>(rec_b(mv, slot)) =
+        u32x4{(uint32_t)x0, (uint32_t)((uint64_t)x0 >> 32), (uint32_t)x1, (uint32_t)((uint64_t)x1 >> 32)};
+    if (fl) mv.a2[slot] = x2;
+  }
+  ++n_enq;
+}
+
 // One tile of the one-pass sort (the block claims it); returns its index.
 //
 // reserve (stateless batches): no look-back.  A stateless record runs on its
@@ -412,43 +579,21 @@ __device__ __forceinline__ uint32_t onesweep_tile(const SortIn& in, const MboxVi
   int r[SK];
   load_actors<SK>(in, t, a);
   load_cols<A2, MC, SK>(in, t, v0, v1, v2, meth);
-  if constexpr (MODE == 4) resolve_pres<SK>(in, lpres, a, r, mb);
-  else resolve_k<MODE, SK>(in, a, r, mb);
+  os_resolve<MODE, SK>(in, lpres, a, r, mb);
   uint32_t wr[SK];
   // (an ordered batch in 8-B records, !spill: a message whose fields do not fit takes its
   // ring position like any other and is written as an escape record below -- FIFO kept)
-#pragma unroll
-  for (int k = 0; k < SK; ++k) {
-    const bool ok = tile_index<SK>(t, k) < in.M && r[k] == in.rank_self && mb[k] < kMaxMbox;
-    if (!ok) mb[k] = kNoSlot;
-    const uint32_t sh = mb[k] & (S - 1);
-    const uint64_t peers = match_bits(sh, mv.log_s, __ballot(ok));
-    const unsigned below = mbcnt64(peers);
-    const int leader = peers ? __builtin_ctzll(peers) : 0;
-    unsigned old = 0;
-    if (ok && below == 0) {
-      old = wcnt(w, sh);
-      wcnt(w, sh) = old + (unsigned)__popcll(peers);
-    }
-    wr[k] = (unsigned)__shfl((int)old, leader) + below;
-  }
+  os_rank<SK>(in, mv.log_s, t, r, mb, wcnt_all + w * S, wr);
   __syncthreads();
   // per shard: wave offsets within the tile, publish the tile's count, look back for its prefix
-  const uint64_t Q = 1ull << mv.log_q;
   unsigned long long timeouts = 0;
   int sp = 0;
   for (uint32_t s = threadIdx.x; s < S; s += kST) {
-    uint32_t c = 0;
     uint64_t excl = 0;
     unsigned long long* d = desc + (size_t)t * S + s;
-#pragma unroll
-    for (int ww = 0; ww < kST / kWave; ++ww) {
-      const uint32_t x = wcnt(ww, s);
-      wcnt(ww, s) = c;
-      c += x;
-    }
+    const uint32_t c = os_wave_offsets(wcnt_all, S, s);
     if (reserve) {
-      excl = c ? atomicAdd(&mv.resv[s * kResvStride], c) : 0u;  // this tile's run of shard s
+      excl = os_reserve(mv, s, c);  // this tile's run of shard s
     } else if (t == 0) {
       __hip_atomic_exchange(d, desc_word(tag, kDescP, c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
@@ -457,46 +602,19 @@ __device__ __forceinline__ uint32_t onesweep_tile(const SortIn& in, const MboxVi
       __hip_atomic_exchange(d, desc_word(tag, kDescP, excl + c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (!reserve && t == in.tiles - 1) gsum[s] = (uint32_t)(excl + c);  // the epoch's total of shard s
-    const uint64_t tl = *ctr_tail(mv, s), hd = *ctr_head(mv, s);
-    const uint64_t free = hd + Q > tl ? hd + Q - tl : 0;
-    const uint32_t rm = (uint32_t)(free < 0xffffffffull ? free : 0xffffffffull);
+    uint64_t tl;
+    const uint32_t rm = os_ring_room(mv, s, tl);
     base[s] = tl;
     room[s] = rm;
     pre[s] = (uint32_t)excl;
-    sp |= excl + c > rm;
-    if (tinfo) {
-      const uint32_t cc = excl >= rm ? 0u : (uint32_t)min((uint64_t)c, rm - excl);
-      tinfo[(size_t)t * 2 * S + s] = (uint32_t)(tl + excl) + shard_rot(mv, s);
-      tinfo[(size_t)t * 2 * S + S + s] = cc | (excl + c > rm ? kRunSpilled : 0u);
-    }
+    sp |= os_run_info(mv, tinfo, t, S, s, tl, rm, excl, c);
   }
   // (in.rec8) the messages whose fields do not fit an 8-B record -- they spill -- and
   // the tile's fields OR-ed (their bit lengths size the next Send's records)
-  uint32_t escm = 0;
   const uint32_t w8 = in.rec8 ? *in.r8w : 0u;  // this Send's 8-B field widths (recw: none, nothing escapes)
-  uint64_t or_m = 0, or_0 = 0, or_1 = 0;
   const bool maxima = in.rec8 || in.recw;  // (wide pure records keep the maxima: back to 8 B once they fit)
-  if (maxima) {
-    const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu, w1 = (w8 >> 16) & 0xffu;
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      if (mb[k] == kNoSlot) continue;
-      const uint64_t z0 = ((uint64_t)v0[k] << 1) ^ (uint64_t)(v0[k] >> 63);
-      const uint64_t z1 = ((uint64_t)v1[k] << 1) ^ (uint64_t)(v1[k] >> 63);
-      or_m |= mb[k], or_0 |= z0, or_1 |= z1;
-      if (in.rec8 && ((mb[k] >> wm) != 0 || (z0 >> w0) != 0 || (z1 >> w1) != 0)) escm |= 1u << k;
-    }
-  }
+  const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
   sp |= escm != 0;
-  if (maxima) {  // the tile's field bit lengths (read by thread 0 past the spill barrier)
-    const uint32_t bm = wave_max_u32(bitlen64(or_m)), b0 = wave_max_u32(bitlen64(or_0)),
-                   b1 = wave_max_u32(bitlen64(or_1));
-    if (lane == 0) {
-      atomicMax(&tmax[0], bm);
-      atomicMax(&tmax[1], b0);
-      atomicMax(&tmax[2], b1);
-    }
-  }
   bool tile_spill = false;
   if (spill) tile_spill = __syncthreads_or(sp) != 0;
   else __syncthreads();
@@ -510,57 +628,8 @@ __device__ __forceinline__ uint32_t onesweep_tile(const SortIn& in, const MboxVi
   for (int k = 0; k < SK; ++k) {
     const int64_t i = tile_index<SK>(t, k);
     if (i >= in.M) continue;
-    const uint32_t origin = in.origin_base + (uint32_t)i;
-    if (mb[k] == kNoSlot) {
-      ++n_miss;
-      if (wsidx) sidx[i] = kNoSlot;
-      write_status(rv, origin, kStatusNoActor);
-      continue;
-    }
-    const uint32_t sh = mb[k] & (S - 1);
-    const uint32_t off = pre[sh] + wcnt(w, sh) + wr[k];
-    const bool esc = (escm >> k) & 1u;  // the record would not fit 8 B
-    if (off >= room[sh] || (esc && spill)) {  // the ring is full (or a stateless record spills)
-      if (spill) {  // the drain runs it from the batch: its route word is all it needs from here
-        ++n_spill;
-        sidx[i] = kSpillSlot;
-        rw[i] = mb[k];
-        continue;
-      }
-      ++n_ovf;
-      if (wsidx) sidx[i] = kNoSlot;
-      write_status(rv, origin, kStatusOverflow);
-      continue;
-    }
-    const uint64_t slot = slot_at(mv, sh, base[sh] + off);
-    if (wsidx) sidx[i] = (uint32_t)slot;
-    const uint32_t mt = meth[k];
-    if (in.recw) {  // wide pure record: {a0, a1} whole, the place in the tile beside it
-      *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-          u32x4{(uint32_t)v0[k], (uint32_t)((uint64_t)v0[k] >> 32), (uint32_t)v1[k], (uint32_t)((uint64_t)v1[k] >> 32)};
-      rec_place(mv)[slot] = (uint16_t)(i & ((kST * SK) - 1));
-    } else if (in.rec8 && esc) {  // (ordered) escape: the place in the tile + bit 63, the fields aside
-      reinterpret_cast<uint64_t*>(mv.rec)[slot] = (uint64_t)(i & ((kST * SK) - 1)) | (1ull << 63);
-      *reinterpret_cast<u32x4*>(in.r8esc + 2 * slot) =
-          u32x4{(uint32_t)v0[k], (uint32_t)((uint64_t)v0[k] >> 32), mb[k], 0u};
-    } else if (in.rec8) {  // 8-B record (uniform method; stateless records that do not fit spilled above)
-      const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu;
-      const uint64_t z0 = ((uint64_t)v0[k] << 1) ^ (uint64_t)(v0[k] >> 63);
-      const uint64_t z1 = ((uint64_t)v1[k] << 1) ^ (uint64_t)(v1[k] >> 63);
-      reinterpret_cast<uint64_t*>(mv.rec)[slot] =
-          (uint64_t)(i & ((kST * SK) - 1)) | ((uint64_t)mb[k] << 12) | (z0 << (12 + wm)) | (z1 << (12 + wm + w0));
-    } else if (mt < 128u && fits_i32(v0[k]) && fits_i32(v1[k]) && v2[k] == 0) {
-      *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-          u32x4{origin | kCompactMark, mb[k] | (mt << 24), (uint32_t)v0[k], (uint32_t)v1[k]};
-    } else {
-      const uint32_t fl = v2[k] != 0 ? (uint32_t)kFlagA2 : 0u;
-      *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-          u32x4{origin | kCompactMark, mb[k] | kCompactLong, (mt & 0xffffu) | (fl << 16), 0u};
-      *reinterpret_cast<u32x4*>(rec_b(mv, slot)) =
-          u32x4{(uint32_t)v0[k], (uint32_t)((uint64_t)v0[k] >> 32), (uint32_t)v1[k], (uint32_t)((uint64_t)v1[k] >> 32)};
-      if (fl) mv.a2[slot] = v2[k];
-    }
-    ++n_enq;
+    os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wr[k], v0[k], v1[k], v2[k], meth[k],
+                     (escm >> k) & 1u, w8, spill, wsidx, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
   }
   // the tile's field bit lengths, for the next Send's widths (rec8_next): a memory-side write
   // (the fused kernel's last block reads it within the launch: its ticket follows a vmcnt(0) wait)
@@ -579,6 +648,147 @@ __global__ __launch_bounds__(kST) void mbx_onesweep_kernel(SortIn in, MboxView m
                                                            bool all_sidx, bool reserve) {
   extern __shared__ __align__(16) unsigned char smem_os[];
   (void)onesweep_tile<MODE, A2, MC>(in, mv, desc, tctr, gsum, sidx, tinfo, rw, rv, spill, all_sidx, smem_os, reserve);
+}
+
+// ---------------------------------------------------------------- K2s persistent reserving sort
+// The reserving one-pass sort of a presence-map Send (route mode 4) as a grid of
+// resident blocks, each walking several tiles (tune mbox_persist).  What a tile of
+// mbx_onesweep_kernel<4> repeats and a Send needs once is done once per block: the map
+// staged in LDS, each ring's tail and room read, the enqueue counters added.  And the
+// tile's serial chain of round trips is shortened by running one tile ahead on the cheap
+// column: tile i+1's actor loads are issued before tile i's record stores, it is resolved
+// and ranked right after them, and its runs' reservations (one returning atomic per shard)
+// come back behind tile i+1's argument loads.  Only the next tile's actors / mailboxes and
+// packed ranks (12 registers) cross an iteration; the arguments are never loaded a tile
+// ahead (the 208-VGPR form, profiles/r5_mailbox_ab.md).  The prefixes and wave offsets are
+// double-buffered in LDS, so a tile costs two barriers.
+//
+// Tiles: no counter, no flag, no block waits for another.  Block b of G (a multiple of 8
+// where there are 8 or more) sits on XCD b % 8; with a tile count that is a multiple of 8
+// it takes tiles x * T/8 + j, j = b / 8 + i * G/8 -- the XCD virt_block gives each tile in
+// the one-tile-per-block form, which is where the ring drain reads its runs.  Otherwise
+// tile b + i * G.  A tile's runs land in the rings in the order the blocks reserve them,
+// which a stateless ring allows (see onesweep_tile).
+__host__ __device__ constexpr size_t persist_lds_bytes(uint32_t S) {
+  return (size_t)S * (8 + 4 + 2 * 4 + 2 * 4 * (kST / kWave));
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx,
+                                                               uint32_t* __restrict__ tinfo, uint32_t* __restrict__ rw,
+                                                               ReplyView rv) {
+  constexpr int SK = kSK;
+  extern __shared__ __align__(16) unsigned char smem_ps[];
+  const uint32_t S = 1u << mv.log_s;
+  unsigned long long* base = reinterpret_cast<unsigned long long*>(smem_ps);  // each ring's epoch-start tail
+  uint32_t* room = reinterpret_cast<uint32_t*>(base + S);                     // offset limit past the tail
+  uint32_t* pre2 = room + S;                                                  // [2][S] a tile's prefix per shard
+  uint32_t* wcnt2 = pre2 + 2 * S;                                             // [2][kST / kWave][S]
+  uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_ps + ((persist_lds_bytes(S) + 15) & ~(size_t)15));
+  __shared__ uint32_t tmax[3];
+  const unsigned w = threadIdx.x / kWave, lane = lane_id();
+  // this block's tiles: first, first + stride, ... (n of them)
+  const uint32_t G = gridDim.x, T = in.tiles;
+  uint32_t first = blockIdx.x, stride = G, n = blockIdx.x < T ? (T - blockIdx.x + G - 1) / G : 0u;
+  if (G >= 8 && (G & 7) == 0 && (T & 7) == 0) {
+    const uint32_t j = blockIdx.x >> 3, T8 = T >> 3;
+    stride = G >> 3;
+    first = (blockIdx.x & 7) * T8 + j;
+    n = j < T8 ? (T8 - j + stride - 1) / stride : 0u;
+  }
+  if (n == 0) return;
+  // once per block: the map, the rings' tails and room
+  stage_pres(in, lpres);
+  for (uint32_t s = threadIdx.x; s < S; s += kST) {
+    uint64_t tl;
+    room[s] = os_ring_room(mv, s, tl);
+    base[s] = tl;
+  }
+  if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
+  for (uint32_t s = lane; s < S; s += kWave) wcnt2[w * S + s] = 0;
+  __syncthreads();
+  const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
+  const bool maxima = in.rec8 || in.recw;
+  uint32_t n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;  // (a block's share of a batch: below 2^32)
+  // the first tile, up to its reservations in flight
+  uint32_t nx[SK];  // the coming tile: actors, then mailboxes
+  PackedRanks<SK> wrp;
+  {
+    uint32_t a[SK], wr[SK];
+    int r[SK];
+    load_actors<SK>(in, first, a);
+    os_resolve<4, SK>(in, lpres, a, r, nx);
+    os_rank<SK>(in, mv.log_s, first, r, nx, wcnt2 + w * S, wr);
+#pragma unroll
+    for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+  }
+  __syncthreads();
+  // (S <= kST: a shard's thread keeps its run's count and reserved offset in registers)
+  uint32_t rc = 0, rx = 0;
+  if (threadIdx.x < S) {
+    rc = os_wave_offsets(wcnt2, S, threadIdx.x);
+    rx = os_reserve(mv, threadIdx.x, rc);
+  }
+  for (uint32_t it = 0; it < n; ++it) {
+    const uint32_t t = first + it * stride, b = it & 1;
+    uint32_t* pre = pre2 + b * S;
+    uint32_t* wcnt_all = wcnt2 + b * (kST / kWave) * S;
+    uint32_t mb[SK], meth[SK];
+    int64_t v0[SK], v1[SK], v2[SK];
+#pragma unroll
+    for (int k = 0; k < SK; ++k) mb[k] = nx[k];
+    // the tile's arguments, then the next tile's actors (in flight across this tile's stores); the tile's
+    // reservations, issued a tile ago, return behind them
+    load_cols<false, false, SK>(in, t, v0, v1, v2, meth);
+    const bool more = it + 1 < n;
+    if (more) load_actors<SK>(in, t + stride, nx);
+    int sp = 0;
+    if (threadIdx.x < S) {
+      const uint32_t s = threadIdx.x;
+      pre[s] = rx;
+      sp = os_run_info(mv, tinfo, t, S, s, base[s], room[s], rx, rc);
+    }
+    const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
+    sp |= escm != 0;
+    const bool tile_spill = __syncthreads_or(sp) != 0;
+    if (threadIdx.x == 0) {
+      // (a tile spilled by its records' widths: flagged for the drains, as in onesweep_tile)
+      if (tile_spill) tinfo[(size_t)t * 2 * S + S] |= kRunSpilled;
+      if (maxima) {  // the tile's field bit lengths; cleared for the next tile (its maxima follow a barrier)
+        (void)atomicExch(&in.r8max[t], tmax[0] | (tmax[1] << 8) | (tmax[2] << 16));
+        tmax[0] = tmax[1] = tmax[2] = 0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SK; ++k) {
+      const int64_t i = tile_index<SK>(t, k);
+      if (i >= in.M) continue;
+      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], v2[k], meth[k],
+                       (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
+    }
+    if (more) {
+      // the next tile in the other buffer (last read before this tile's barrier): resolved, ranked, reserved
+      uint32_t* wnext = wcnt2 + (b ^ 1) * (kST / kWave) * S;
+      for (uint32_t s = lane; s < S; s += kWave) wnext[w * S + s] = 0;
+      uint32_t a[SK], wr[SK];
+      int r[SK];
+#pragma unroll
+      for (int k = 0; k < SK; ++k) a[k] = nx[k];
+      os_resolve<4, SK>(in, lpres, a, r, nx);
+      os_rank<SK>(in, mv.log_s, t + stride, r, nx, wnext + w * S, wr);
+#pragma unroll
+      for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+      __syncthreads();
+      if (threadIdx.x < S) {
+        rc = os_wave_offsets(wnext, S, threadIdx.x);
+        rx = os_reserve(mv, threadIdx.x, rc);
+      }
+    }
+  }
+  // once per block: the enqueue counters
+  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_ovf, kMbOverflow, n_miss, kMbNoActor);
+  __syncthreads();  // block_add_stats' LDS partials are reused
+  block_add_stats(mv.stats, n_spill, kMbSpilled, 0, -1, 0, -1);
 }
 
 // ---------------------------------------------------------------- compact record decode

@@ -15,6 +15,10 @@
 //   mbox_fused        -1       stateless world-1 mailbox Sends: fused sort + drain kernel
 //                              (-1: up to 512 tiles, 0 never, 1 always)
 //   mbox_rec8         -1       8-B ring records (-1: batches past 512 tiles, 0 never, 1 always)
+//   mbox_persist      -1       presence-map (route mode 4) reserving sort as resident blocks that walk
+//                              the tiles: map staged, ring room read and counters added once per
+//                              block (-1: batches past 512 tiles, 0 never -- one block per tile, the
+//                              reference of tests/test_mailbox_persist_gpu.py -- 1 always)
 //   mbox_sort         0        mailbox sort: 0 auto, 1 one-pass, 2 count + scatter
 //   mbox_drain_msg    0        stateless drain in message order instead of ring order
 //   sx_sort           0        sorted exchange, rank-only batches: 0 reserving one pass,
@@ -39,6 +43,7 @@ namespace ptype {
 struct Tune {
   int mbox_fused = -1;
   int mbox_rec8 = -1;
+  int mbox_persist = -1;
   int mbox_sort = 0;
   int mbox_drain_msg = 0;
   int sx_sort = 0;
@@ -57,6 +62,7 @@ struct Tune {
     };
     if (k == "mbox_fused") return i(mbox_fused);
     if (k == "mbox_rec8") return i(mbox_rec8);
+    if (k == "mbox_persist") return i(mbox_persist);
     if (k == "mbox_sort") return i(mbox_sort);
     if (k == "mbox_drain_msg") return i(mbox_drain_msg);
     if (k == "sx_sort") return i(sx_sort);

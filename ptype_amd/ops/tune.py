@@ -19,7 +19,8 @@ keys (read when an exchange is built or per Send):
   auto_arrival     1        world-1 mailbox Sends without ordered methods, up to 2 Mi
                             messages: arrival rings (0: the actor-sharded sort)
 
-The native keys are listed in csrc/hip/tune.hpp; ``set`` forwards them.
+The native keys (``mbox_fused``, ``mbox_rec8``, ``mbox_persist``, ``mbox_sort``, ...) are listed
+in csrc/hip/tune.hpp; ``set`` forwards them.
 """
 from __future__ import annotations
 
