@@ -201,7 +201,7 @@ class Client:
     def Go(self, serviceMethod: str, args: Any, done: CallChannel | None = None):
         return self._c.go(serviceMethod, args, done)
 
-    def Send(self, batch, retries: int | None = None, retry_on=None, **kw):
+    def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -228,11 +228,22 @@ class Client:
         the replies are final.  ``None`` follows the runtime's setting, ``False``
         skips this Send, ``True`` without a ledger raises.  An accounted Send does
         not defer its overflow re-sends, and the ledger is the caller's view: each
-        rank accounts the batches it sent."""
+        rank accounts the batches it sent.
+
+        ``coalesce``: Go's ``singleflight`` on the batch -- messages of a pure method
+        (``Calculator.Multiply``, ``Prime.Check``, ``Echo``) with equal ``(actor,
+        method, a0, a1, a2)`` are sent once and every duplicate gets that reply, so
+        the result equals the plain Send's element for element (ops/coalesce.py).
+        ``None`` follows ``gpu.coalesce``, ``False`` skips this Send.  It costs a
+        hash pass over the batch and one host read per Send, is refused under graph
+        capture and never defers its overflow re-sends;
+        ``Stats()["runtime"]["coalesce"]`` counts messages and executed leaders."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
             kw.update(retries=int(retries), retry_on=retry_on)
+        if coalesce is not None:
+            kw.update(coalesce=bool(coalesce))
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

@@ -331,6 +331,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("mailbox_shards", &GpuConfig::mailbox_shards)
       .def_readwrite("mailbox_slots", &GpuConfig::mailbox_slots)
       .def_readwrite("ledger", &GpuConfig::ledger)
+      .def_readwrite("coalesce", &GpuConfig::coalesce)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

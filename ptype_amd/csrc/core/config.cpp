@@ -130,6 +130,7 @@ void decode_ptype(const YNode& root, Config& c) {
         else if (g.first == "mailbox_slots") c.gpu.mailbox_slots = (uint32_t)want_int(G, g.first, g.second);
         else if (g.first == "watch") c.gpu.watch = want_bool(G, g.first, g.second);
         else if (g.first == "ledger") c.gpu.ledger = want_bool(G, g.first, g.second);
+        else if (g.first == "coalesce") c.gpu.coalesce = want_bool(G, g.first, g.second);
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

@@ -63,6 +63,7 @@ struct GpuConfig {
   std::string comm = "rccl";
   bool watch = true;          // follow the store (shard records, leases) into the GPU registry mirror
   bool ledger = false;        // Send ledger in HBM (ops/ledger.py): per-method counts, reply digest, audit
+  bool coalesce = false;      // Send coalesces duplicate pure calls by default (ops/coalesce.py)
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

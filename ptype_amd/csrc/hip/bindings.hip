@@ -8,6 +8,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "coalesce.hpp"
 #include "common.hpp"
 #include "engine.hpp"
 #include "exchange_sorted.hpp"
@@ -88,6 +89,15 @@ void launch_retry_merge(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uin
 int64_t ledger_tile();
 void launch_ledger_account(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t,
                            uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
+int64_t coalesce_tile();
+int64_t coalesce_select_tile();
+void launch_coalesce_group(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int,
+                           uintptr_t, uintptr_t);
+void launch_coalesce_select(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                            uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                            uintptr_t);
+void launch_coalesce_fanout(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t,
+                            uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -294,6 +304,29 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("load"), py::arg("n_load"), py::arg("ticket"), py::arg("stream"),
         "one pass over a Send's replies and batch columns into ledger (copies x words of ledger_words() int64), the optional "
         "per-actor load table (n_load int64) and sends; ticket: ledger_words()['ticket_words'] zeroed u32");
+
+  // ---- Send coalescing (coalesce.hip, coalesce.hpp): duplicates of a pure call are sent once
+  m.def("coalesce_tile", &coalesce_tile, "messages per block of coalesce_group's insert kernel");
+  m.def("coalesce_select_tile", &coalesce_select_tile, "messages per block of coalesce_select");
+  m.def("coalesce_pure", [](uint32_t method) { return method_pure(method & 0xffffu); }, py::arg("method"),
+        "whether duplicates of this method are coalesced (coalesce.hpp)");
+  m.def("coalesce_hash", [](uint32_t actor, uint32_t method, int64_t a0, int64_t a1, int64_t a2) {
+    return coalesce_hash(actor, method, a0, a1, a2);
+  }, py::arg("actor"), py::arg("method"), py::arg("a0"), py::arg("a1"), py::arg("a2"), "the key hash (coalesce.hpp)");
+  m.def("coalesce_group", &launch_coalesce_group, py::arg("actor"), py::arg("method_col"), py::arg("method_uniform"),
+        py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("M"), py::arg("table"), py::arg("table_log2"),
+        py::arg("lead"), py::arg("stream"),
+        "lead[i] = the lowest j whose (actor, method, a0, a1, a2) equals message i's, for a pure method; i otherwise. "
+        "table: 1 << table_log2 u32 words of workspace (>= 2 M), cleared on the stream");
+  m.def("coalesce_select", &launch_coalesce_select, py::arg("lead"), py::arg("M"), py::arg("actor"), py::arg("a0"),
+        py::arg("a1"), py::arg("a2"), py::arg("method"), py::arg("idx"), py::arg("pos"), py::arg("actor_out"),
+        py::arg("a0_out"), py::arg("a1_out"), py::arg("a2_out"), py::arg("method_out"), py::arg("counts"),
+        py::arg("k_out"), py::arg("stream"),
+        "stable compaction of the messages with lead[i] == i: idx (ascending), the gathered rows of every non-null "
+        "column, pos[i] = i's row (-1 for a follower), K in k_out[0]; counts: ceil(M / coalesce_select_tile()) u32");
+  m.def("coalesce_fanout", &launch_coalesce_fanout, py::arg("val"), py::arg("st"), py::arg("M"), py::arg("lead"),
+        py::arg("pos"), py::arg("v2"), py::arg("s2"), py::arg("K"), py::arg("stream"),
+        "val[i] = v2[pos[lead[i]]], st[i] = s2[pos[lead[i]]] for i < M");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

@@ -21,6 +21,10 @@ METHOD_COORD_PRIME = 0x7D
 FOLD_MUL = 0x100000001B3
 ORDERED_METHODS = frozenset({METHOD_SEQ_FOLD})  # one at a time per actor, in mailbox order
 
+# reply = f(a0, a1, a2), status = f(the actor exists): duplicates in one Send may be coalesced
+# (ops/coalesce.py; the device-side twin is method_pure in csrc/hip/coalesce.hpp)
+PURE_METHODS = frozenset({METHOD_CALC_MULTIPLY, METHOD_PRIME_CHECK, METHOD_ECHO})
+
 
 def method_ordered(m: int) -> bool:
     return int(m) in ORDERED_METHODS

@@ -72,7 +72,7 @@ class DeviceRuntime:
                  delay_us: int = 0, max_batch: int = 1 << 20, chunks: int = 0, random_state: bool = False,
                  group=None, shm: bool = True, service: str = "", mailbox_shards: int = 256,
                  mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0,
-                 ledger: bool = False):
+                 ledger: bool = False, coalesce: bool = False):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -137,6 +137,10 @@ class DeviceRuntime:
             from .ops.ledger import Ledger
 
             self.ledger = Ledger(self.device, actors=self.total_actors)
+        # Send coalescing (ops/coalesce.py): the default of send(coalesce=None), the grouping
+        # workspace with its host counters (created by the first coalesced Send)
+        self.coalesce = bool(coalesce)
+        self._coalescer = None
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -200,7 +204,7 @@ class DeviceRuntime:
         rt = cls(device_for_rank(rank), actors=g.actors, ring=g.ring, idle_ms=g.idle_ms, delay_us=g.delay_us,
                  max_batch=g.max_batch, service=cfg.service_name, mailbox_shards=g.mailbox_shards,
                  mailbox_slots=g.mailbox_slots, delivery=g.delivery, comm=g.comm,
-                 comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger)
+                 comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger, coalesce=g.coalesce)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -344,7 +348,47 @@ class DeviceRuntime:
         return ReplicaRouter(service, self.world0, la, max_connections, kv=self._kv)
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
-             retries: int | None = None, retry_on=None, account: bool | None = None):
+             retries: int | None = None, retry_on=None, account: bool | None = None,
+             coalesce: bool | None = None):
+        """Batched Send (``_send``), optionally coalesced.
+        ``coalesce``: duplicate calls of a pure method (``records.PURE_METHODS``) in
+        this batch -- equal ``(logical actor id, method, a0, a1, a2)`` -- are sent once
+        and every duplicate gets the reply of the group's first message
+        (ops/coalesce.py: Go's ``singleflight`` per Send).  None follows the runtime's
+        setting (``DeviceRuntime(coalesce=...)``, ``gpu.coalesce``), False skips this
+        Send.  The batch is grouped on the ids its caller wrote, before any ``router``;
+        the leaders go through the whole Send below as one sub-batch in message order
+        (one collective Send per rank whatever its K; retries, the router, the elastic
+        loop and the overflow re-sends apply to the leaders, and a follower inherits its
+        leader's final status, whatever it is); the Send ledger accounts the full batch
+        once, on the fanned-out replies.  A batch without duplicates is sent as it is.
+        A coalesced Send reads K on the host, so it is refused under graph capture, and
+        it never defers its overflow re-sends.  The result equals, element for element,
+        what the same Send returns without ``coalesce``."""
+        if coalesce is None:
+            coalesce = self.coalesce
+        if not coalesce:
+            return self._send(service, batch, resend_overflow, router, retries, retry_on, account)
+        if account and self.ledger is None:
+            raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
+                             "gpu.ledger)")
+        if (self._exchange is not None and self._exchange._capturing) or (
+                self.on_gpu and torch.cuda.is_current_stream_capturing()):
+            raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
+        if self._coalescer is None:
+            from .ops.coalesce import Coalescer
+
+            self._coalescer = Coalescer(self.device, self.max_batch)
+        ledger = self.ledger if account is None or account else None
+        # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
+        out, _ = self._coalescer.send(batch, lambda sub: self._send(
+            service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+        if ledger is not None:
+            ledger.account(batch, out[0], out[1])
+        return out
+
+    def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
+              retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False):
         """Batched Send: every message to its actor anywhere in the node and the
         replies back in message order.  Collective across the process group.
         Registry changes seen since the last Send are applied first.  With an
@@ -359,7 +403,9 @@ class DeviceRuntime:
         ``gpu.ledger``) accounts this Send -- once, on its final replies, under the
         batch's logical actor ids.  None follows the runtime's setting, False skips
         this Send, True without a ledger raises.  An accounted Send does not defer
-        its overflow re-sends."""
+        its overflow re-sends.
+        ``final``: the replies must be final on return (a coalesced Send fans them
+        out): the overflow re-sends are not deferred."""
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
@@ -389,7 +435,7 @@ class DeviceRuntime:
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
             if rkw:
                 return ex.send_all(batch, logical=logical, **rkw)
-            return ex.send_all(batch, defer=self.world > 1) if resend_overflow else ex.send(batch)
+            return ex.send_all(batch, defer=self.world > 1 and not final) if resend_overflow else ex.send(batch)
         from .parallel.elastic import RankFailure, is_rank_failure
 
         dp = self.group.dp if self._native else None  # the compiled lifecycle (watchdog, recovery)
@@ -779,6 +825,8 @@ class DeviceRuntime:
             out["exchange"] = asdict(self._exchange.stats())
         if self.ledger is not None:
             out["ledger"] = self.ledger.read()
+        out["coalesce"] = (dict(self._coalescer.counters) if self._coalescer is not None
+                           else {"sends": 0, "messages": 0, "executed": 0})
         return out
 
     def close(self) -> None:
