@@ -201,7 +201,8 @@ class Client:
     def Go(self, serviceMethod: str, args: Any, done: CallChannel | None = None):
         return self._c.go(serviceMethod, args, done)
 
-    def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None, **kw):
+    def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None,
+             cache: bool | None = None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -237,13 +238,31 @@ class Client:
         ``None`` follows ``gpu.coalesce``, ``False`` skips this Send.  It costs a
         hash pass over the batch and one host read per Send, is refused under graph
         capture and never defers its overflow re-sends;
-        ``Stats()["runtime"]["coalesce"]`` counts messages and executed leaders."""
+        ``Stats()["runtime"]["coalesce"]`` counts messages and executed leaders.
+
+        ``cache``: the cache a Go service keeps next to ``singleflight`` -- a call of a
+        pure method whose ``STATUS_OK`` reply an earlier cached Send of this process
+        stored (same key) is answered from the HBM reply cache and not sent
+        (ops/reply_cache.py); only the misses travel, after coalescing if both are
+        on.  The result equals the plain Send's element for element: a non-OK reply
+        is never stored, any other method runs as often as it appears, and the
+        cache is cleared whenever the registry (or this client's replica set)
+        changed since the last cached Send.  ``None`` follows ``gpu.cache``, ``False``
+        skips this Send; ``gpu.cache_entries`` sizes the direct-mapped table (64 B
+        per entry, default ``1 << 20``).  It costs one read-only probe per message
+        and one host read per Send, is refused under graph capture and never defers;
+        ``Stats()["runtime"]["cache"]`` counts messages, hits and misses sent.  The
+        cache belongs to the process's runtime: cached Sends must all be issued on one
+        stream, and clients of different replicated services (different routers)
+        that alternate on it clear it on every Send."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
             kw.update(retries=int(retries), retry_on=retry_on)
         if coalesce is not None:
             kw.update(coalesce=bool(coalesce))
+        if cache is not None:
+            kw.update(cache=bool(cache))
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

@@ -332,6 +332,8 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("mailbox_slots", &GpuConfig::mailbox_slots)
       .def_readwrite("ledger", &GpuConfig::ledger)
       .def_readwrite("coalesce", &GpuConfig::coalesce)
+      .def_readwrite("cache", &GpuConfig::cache)
+      .def_readwrite("cache_entries", &GpuConfig::cache_entries)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

@@ -131,6 +131,12 @@ void decode_ptype(const YNode& root, Config& c) {
         else if (g.first == "watch") c.gpu.watch = want_bool(G, g.first, g.second);
         else if (g.first == "ledger") c.gpu.ledger = want_bool(G, g.first, g.second);
         else if (g.first == "coalesce") c.gpu.coalesce = want_bool(G, g.first, g.second);
+        else if (g.first == "cache") c.gpu.cache = want_bool(G, g.first, g.second);
+        else if (g.first == "cache_entries") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n <= 0) fail(Errc::kConfig, "gpu.cache_entries must be positive");
+          c.gpu.cache_entries = (uint64_t)n;
+        }
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

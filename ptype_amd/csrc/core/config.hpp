@@ -64,6 +64,8 @@ struct GpuConfig {
   bool watch = true;          // follow the store (shard records, leases) into the GPU registry mirror
   bool ledger = false;        // Send ledger in HBM (ops/ledger.py): per-method counts, reply digest, audit
   bool coalesce = false;      // Send coalesces duplicate pure calls by default (ops/coalesce.py)
+  bool cache = false;         // Send answers pure calls from the HBM reply cache by default (ops/reply_cache.py)
+  uint64_t cache_entries = 1 << 20;  // reply cache entries (64 B each; rounded up to a power of two, [16, 1 << 26])
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

@@ -15,6 +15,7 @@
 #include "ipc_comm.hpp"
 #include "ledger.hpp"
 #include "mailbox.hpp"
+#include "reply_cache.hpp"
 #include "server.hpp"
 #include "xcall.hpp"
 #include "gob_bridge.hpp"
@@ -98,6 +99,14 @@ void launch_coalesce_select(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t,
                             uintptr_t);
 void launch_coalesce_fanout(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t,
                             uintptr_t);
+int64_t reply_cache_tile();
+void launch_reply_cache_lookup(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int,
+                               uint32_t, uintptr_t, uintptr_t, uintptr_t);
+void launch_reply_cache_insert(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t,
+                               uintptr_t, uintptr_t, int, uint32_t, uint32_t, uintptr_t);
+void launch_reply_cache_insert_phase(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t,
+                                     uintptr_t, uintptr_t, int, uint32_t, uint32_t, int, uintptr_t);
+void launch_reply_cache_clear(uintptr_t, int, uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -327,6 +336,28 @@ PYBIND11_MODULE(_hip, m) {
   m.def("coalesce_fanout", &launch_coalesce_fanout, py::arg("val"), py::arg("st"), py::arg("M"), py::arg("lead"),
         py::arg("pos"), py::arg("v2"), py::arg("s2"), py::arg("K"), py::arg("stream"),
         "val[i] = v2[pos[lead[i]]], st[i] = s2[pos[lead[i]]] for i < M");
+
+  // ---- reply cache (reply_cache.hip, reply_cache.hpp): pure calls answered from HBM across Sends
+  m.def("reply_cache_tile", &reply_cache_tile, "messages per block of reply_cache_lookup");
+  m.attr("REPLY_CACHE_PENDING") = (int)kReplyCachePending;
+  m.def("reply_cache_lookup", &launch_reply_cache_lookup, py::arg("actor"), py::arg("method_col"),
+        py::arg("method_uniform"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("M"), py::arg("table"),
+        py::arg("table_log2"), py::arg("epoch"), py::arg("val"), py::arg("st"), py::arg("stream"),
+        "a pure message whose key the table holds at this epoch: val[i] = the stored value, st[i] = STATUS_OK; any "
+        "other message: st[i] = REPLY_CACHE_PENDING.  table: 1 << table_log2 entries of 64 B");
+  m.def("reply_cache_insert", &launch_reply_cache_insert, py::arg("actor"), py::arg("method_col"),
+        py::arg("method_uniform"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("K"), py::arg("val"),
+        py::arg("st"), py::arg("table"), py::arg("table_log2"), py::arg("epoch"), py::arg("seq"), py::arg("stream"),
+        "the pure STATUS_OK rows of a sub-batch into the table (the claim launch, then the write launch): per slot "
+        "the lowest row of this insert wins; seq must rise by one per insert");
+  m.def("reply_cache_insert_phase", &launch_reply_cache_insert_phase, py::arg("actor"), py::arg("method_col"),
+        py::arg("method_uniform"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("K"), py::arg("val"),
+        py::arg("st"), py::arg("table"), py::arg("table_log2"), py::arg("epoch"), py::arg("seq"), py::arg("phase"),
+        py::arg("stream"),
+        "MEASUREMENT ONLY (tools/reply_cache_cost.py): one launch of reply_cache_insert alone, phase 1 the claim, 2 the "
+        "write.  A write without its claim, or a reused seq, breaks the table's replacement rule: never on a live cache");
+  m.def("reply_cache_clear", &launch_reply_cache_clear, py::arg("table"), py::arg("table_log2"), py::arg("stream"),
+        "every entry: zero, claim all ones, epoch 0");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

@@ -71,7 +71,13 @@ def select(batch: MsgBatch, status: torch.Tensor, retry_on=DEFAULT_RETRY_ON):
     ``torch.nonzero`` returns) and ``sub`` the K gathered rows of every column.
     On a GPU the outputs are views of M-row buffers, since K is known only after
     the kernels ran."""
-    mask = retry_mask(retry_on)
+    return select_mask(batch, status, retry_mask(retry_on))
+
+
+def select_mask(batch: MsgBatch, status: torch.Tensor, mask: int):
+    """``select`` by a raw 32-bit mask (bit s set: status s is selected), unvalidated:
+    the reply cache compacts its misses by a marker status of its own
+    (ops/reply_cache.py)."""
     M = batch.M
     if status.dtype != torch.int32 or status.numel() != M:
         raise TypeError("select: status must be int32[M]")

@@ -54,6 +54,7 @@ class ReplicaRouter:
         self.service, self.world, self.local_addr = service, int(world), local_addr
         self.max_connections = int(max_connections)
         self.seq = 0  # calls routed so far (the balancer's round-robin counter)
+        self.changes = 0  # rises when set_records is given a different record set (the reply cache watches it)
         self.mirror = None
         self._records: list[dict] = []
         self.sel: list[int] = []
@@ -70,6 +71,8 @@ class ReplicaRouter:
 
     def set_records(self, records: list[dict]) -> None:
         recs = sorted((r for r in records if r.get("replica")), key=lambda r: str(r.get("node", "")))
+        if recs != self._records:
+            self.changes += 1
         self._records = recs
         self.sel = select_ranks(self.local_addr, recs, self.max_connections) if recs else []
         self.n_logical = min((int(r["count"]) for r in recs), default=0)

@@ -72,7 +72,7 @@ class DeviceRuntime:
                  delay_us: int = 0, max_batch: int = 1 << 20, chunks: int = 0, random_state: bool = False,
                  group=None, shm: bool = True, service: str = "", mailbox_shards: int = 256,
                  mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0,
-                 ledger: bool = False, coalesce: bool = False):
+                 ledger: bool = False, coalesce: bool = False, cache: bool = False, cache_entries: int = 1 << 20):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -141,6 +141,14 @@ class DeviceRuntime:
         # workspace with its host counters (created by the first coalesced Send)
         self.coalesce = bool(coalesce)
         self._coalescer = None
+        # Reply cache (ops/reply_cache.py): the default of send(cache=None), the table with its
+        # host counters (created by the first cached Send), and the registry change counter --
+        # bumped by everything that can change which actors answer; a cached Send that sees it
+        # (or its router's record counter) moved clears the cache first
+        self.cache, self.cache_entries = bool(cache), int(cache_entries)
+        self._cache = None
+        self._registry_changes = 0
+        self._cache_seen = None
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -204,7 +212,8 @@ class DeviceRuntime:
         rt = cls(device_for_rank(rank), actors=g.actors, ring=g.ring, idle_ms=g.idle_ms, delay_us=g.delay_us,
                  max_batch=g.max_batch, service=cfg.service_name, mailbox_shards=g.mailbox_shards,
                  mailbox_slots=g.mailbox_slots, delivery=g.delivery, comm=g.comm,
-                 comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger, coalesce=g.coalesce)
+                 comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger, coalesce=g.coalesce,
+                 cache=g.cache, cache_entries=g.cache_entries)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -231,11 +240,15 @@ class DeviceRuntime:
         self.table.clear()
         self.mirror = RegistryMirror(self.table, kv, service, watch=watch)
         self.mirror.apply()
+        self._registry_changes += 1
         self._kv, self._node = kv, node
 
     def sync(self) -> int:
         """Apply pending registry changes (joins, leaves, lease expiries) now."""
-        return self.mirror.apply() if self.mirror is not None else 0
+        n = self.mirror.apply() if self.mirror is not None else 0
+        if n:
+            self._registry_changes += 1
+        return n
 
     def publish_shard(self, store, service: str, node: str) -> None:
         """Record this rank's actor shard of `service` in the replicated store
@@ -265,12 +278,14 @@ class DeviceRuntime:
             self.table.upsert(actor_keys(ids), torch.full((n,), r, dtype=torch.int32, device=self.device),
                               mbox.to(torch.int32))
             total += n
+        self._registry_changes += 1
         return total
 
     def place_local(self, n_actors_total: int | None = None) -> None:
         """Strided placement without a control plane (single process / bench):
         every rank mirrors every rank's shard."""
         n = self.actors
+        self._registry_changes += 1
         self.table.clear()
         for r in range(self.world):
             mbox = torch.arange(n, dtype=torch.int64, device=self.device)
@@ -304,6 +319,7 @@ class DeviceRuntime:
         several net/rpc services on one server; here they share the GPU actors and
         the registry mirror, and a Send names which one it addresses)."""
         self.hosted.add(service)
+        self._registry_changes += 1
 
     def _check_service(self, service: str | None) -> None:
         if service and self.hosted and service not in self.hosted:
@@ -349,8 +365,8 @@ class DeviceRuntime:
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
              retries: int | None = None, retry_on=None, account: bool | None = None,
-             coalesce: bool | None = None):
-        """Batched Send (``_send``), optionally coalesced.
+             coalesce: bool | None = None, cache: bool | None = None):
+        """Batched Send (``_send``), optionally coalesced and answered from the reply cache.
         ``coalesce``: duplicate calls of a pure method (``records.PURE_METHODS``) in
         this batch -- equal ``(logical actor id, method, a0, a1, a2)`` -- are sent once
         and every duplicate gets the reply of the group's first message
@@ -364,28 +380,83 @@ class DeviceRuntime:
         once, on the fanned-out replies.  A batch without duplicates is sent as it is.
         A coalesced Send reads K on the host, so it is refused under graph capture, and
         it never defers its overflow re-sends.  The result equals, element for element,
-        what the same Send returns without ``coalesce``."""
+        what the same Send returns without ``coalesce``.
+        ``cache``: a call of a pure method whose ``STATUS_OK`` reply an earlier cached
+        Send of this runtime stored -- same key as above -- is answered from the HBM
+        reply cache and not sent (ops/reply_cache.py).  None follows the runtime's
+        setting (``DeviceRuntime(cache=...)``, ``gpu.cache``), False skips this Send.
+        The order is fixed: coalesce, then cache, then the Send below -- the cache sees
+        coalescing's leaders, and retries, the router, the elastic loop and the overflow
+        re-sends see the misses only, as one sub-batch in message order (a non-pure
+        message is always a miss, so an ordered method keeps its per-actor FIFO).  The
+        inner Send runs exactly once per cached Send (a rank whose batch was all hits
+        joins with an empty batch); at world 1 with no miss it is skipped.  A non-OK
+        reply is never stored.  The registry is synced first and the cache cleared when
+        anything that decides whether an actor exists has changed since the last
+        cached Send (``sync`` applying changes, ``recover``, ``restore_from``, ``host``,
+        the router's record set); ``cache_clear()`` does it by hand.  A Send with another
+        ``router`` than the last cached Send's (or with none after one, or the reverse)
+        counts as such a change: clients with different routers that alternate on one
+        runtime clear the cache on every Send and get nothing from it.  Like a coalesced
+        Send it reads K on the host, is refused under graph capture and never defers;
+        the ledger accounts the full batch once, hits included.  The table is state
+        that outlives the Send and stream order is its only protection: every cached
+        Send of a runtime must be issued on the same stream (or on streams the caller
+        orders after one another)."""
         if coalesce is None:
             coalesce = self.coalesce
-        if not coalesce:
+        if cache is None:
+            cache = self.cache
+        if not coalesce and not cache:
             return self._send(service, batch, resend_overflow, router, retries, retry_on, account)
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
         if (self._exchange is not None and self._exchange._capturing) or (
                 self.on_gpu and torch.cuda.is_current_stream_capturing()):
+            if not coalesce:
+                raise ValueError("send(cache=True) inside a captured Send: selecting the misses needs a host read")
             raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
+        ledger = self.ledger if account is None or account else None
+        # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
+        inner = (lambda sub: self._send(service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+        if cache:
+            if self._cache is None:
+                from .ops.reply_cache import ReplyCache
+
+                self._cache = ReplyCache(self.device, self.cache_entries)
+            self.sync()
+            if router is not None:
+                router.refresh()
+            else:
+                self._check_service(service)  # (an all-hit Send never reaches _send's check)
+            # (the router itself is kept, not its id(): a collected router's id can be reused)
+            seen = (self._registry_changes, router, None if router is None else router.changes)
+            last = self._cache_seen
+            if last is None or seen[0] != last[0] or seen[1] is not last[1] or seen[2] != last[2]:
+                if last is not None:
+                    self._cache.clear()
+                self._cache_seen = seen
+            uncached = inner
+            inner = (lambda sub: self._cache.send(sub, uncached, collective=self.world > 1))
+        if not coalesce:
+            out = inner(batch)
+            if ledger is not None:
+                ledger.account(batch, out[0], out[1])
+            return out
         if self._coalescer is None:
             from .ops.coalesce import Coalescer
 
             self._coalescer = Coalescer(self.device, self.max_batch)
-        ledger = self.ledger if account is None or account else None
-        # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
-        out, _ = self._coalescer.send(batch, lambda sub: self._send(
-            service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+        out, _ = self._coalescer.send(batch, inner)
         if ledger is not None:
             ledger.account(batch, out[0], out[1])
         return out
+
+    def cache_clear(self) -> None:
+        """Drop every entry of the reply cache (O(1): the cache's epoch moves on)."""
+        if self._cache is not None:
+            self._cache.clear()
 
     def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
               retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False):
@@ -612,6 +683,7 @@ class DeviceRuntime:
             kept = [self.blocks.index(r) if r in self.blocks else -1 for r in nb]
             self._rehome(own, nb, kept, [k < 0 and r in self.replicas for r, k in zip(nb, kept)])
         self.recoveries += 1
+        self._registry_changes += 1
         _log.warning("data-plane generation %d formed: world %d, lost original ranks %s, hosting %s", m["gen"],
                      self.world, lost, self.blocks)
         trace.mark("ptype.regenerated")
@@ -799,6 +871,7 @@ class DeviceRuntime:
             if self.on_gpu and not ent.is_pinned():
                 ent, exp = ent.pin_memory(), exp.pin_memory()
             self.table.load_packed(ent, exp)
+        self._registry_changes += 1
 
     # ------------------------------------------------------------------ stats / teardown
     def stats(self) -> dict:
@@ -827,6 +900,8 @@ class DeviceRuntime:
             out["ledger"] = self.ledger.read()
         out["coalesce"] = (dict(self._coalescer.counters) if self._coalescer is not None
                            else {"sends": 0, "messages": 0, "executed": 0})
+        out["cache"] = (dict(self._cache.counters, entries=self._cache.entries) if self._cache is not None
+                        else {"sends": 0, "messages": 0, "hits": 0, "sent": 0, "clears": 0, "entries": 0})
         return out
 
     def close(self) -> None:
