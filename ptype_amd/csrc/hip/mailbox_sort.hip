@@ -99,7 +99,9 @@ static uint32_t persist_grid(size_t lds, int64_t tiles) {
 // won), the persistent reserving sort with ONE block per CU that prefetched whole tiles (42.8
 // vs 50.5 G msg/s; the kept one, mbx_persist_sort_kernel, runs two per CU and carries only the
 // next tile's actors and ranks), the tile's store loop as one shared function (5-15 VGPRs more
-// in every sort kernel; profiles/persistent_sort.md), 1024- and 2048-message tiles for the
+// in every sort kernel; profiles/persistent_sort.md), the persistent sort's whole-tile loads
+// on the actor column too and left to the scheduler (133 and 130 VGPRs: three waves per SIMD;
+// profiles/sort_drain_waits.md), 1024- and 2048-message tiles for the
 // fused / separate sort, arguments loaded after the look-back, the LDS-table count,
 // the group look-back, non-temporal directory gathers and reply stores, the binned ordered
 // drain (233 vs 175 us), 2048-record ordered windows, the ordered drain without the

@@ -37,6 +37,10 @@ constexpr uint32_t kNoSlot = 0xffffffffu;
 // FIFO and answer kStatusOverflow (send_all re-sends the tail).
 constexpr uint32_t kSpillSlot = 0xfffffffeu;
 constexpr uint32_t kRunSpilled = 0x80000000u;  // tinfo count word: the run did not fit the ring's room
+// s_waitcnt vmcnt(0) as the builtin's gfx9 immediate (expcnt and lgkmcnt left at their maxima).
+// The builtin, not inline assembly: the compiler's wait insertion reads it and then knows that no
+// load is outstanding, so it adds no waits of its own behind it.
+constexpr int kWaitVmcnt0 = 0x0f70;
 
 template <int MODE>
 __global__ __launch_bounds__(kST) void mbx_count_kernel(SortIn in, uint32_t log_s, uint32_t* __restrict__ hist,
@@ -268,6 +272,35 @@ __device__ __forceinline__ void load_cols(const SortIn& in, uint32_t t, int64_t 
   }
 }
 
+// The persistent sort's argument columns.  A tile that lies wholly inside the batch, with a1
+// present (`full`: every tile of a Multiply batch but its last): the loads without per-item
+// bounds branches, so they issue as one run.  Otherwise the guarded form.  (The 4-B actor
+// column keeps the guarded form on every tile: without its branches the kernel takes 133
+// VGPRs, three waves per SIMD.)
+template <int SK>
+__device__ __forceinline__ bool tile_is_full(const SortIn& in, uint32_t t) {
+  return in.a1 != nullptr && ((int64_t)t + 1) * (kST * SK) <= (int64_t)in.M;
+}
+template <int SK>
+__device__ __forceinline__ void load_args_tile(const SortIn& in, uint32_t t, bool full, int64_t (&v0)[SK],
+                                               int64_t (&v1)[SK]) {
+  if (full) {
+#pragma unroll
+    for (int k = 0; k < SK; ++k) {
+      const int64_t i = tile_index<SK>(t, k);
+      v0[k] = __builtin_nontemporal_load(in.a0 + i);
+      v1[k] = __builtin_nontemporal_load(in.a1 + i);
+    }
+    // (the run stays a run: left to the scheduler, the 16 loads spread over the next tile's resolve and
+    // ranking and the kernel takes 130 VGPRs)
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    int64_t v2[SK];
+    uint32_t meth[SK];
+    load_cols<false, false, SK>(in, t, v0, v1, v2, meth);
+  }
+}
+
 __device__ __forceinline__ uint32_t bitlen64(uint64_t x) { return x ? 64u - (uint32_t)__clzll(x) : 0u; }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
@@ -459,6 +492,16 @@ __device__ __forceinline__ uint32_t os_fields(const SortIn& in, uint32_t w8, con
     atomicMax(&tmax[2], b1);
   }
   return escm;
+}
+
+// The one wait for a tile's loads (the persistent sort): its arguments and the coming tile's
+// actors used here, on every path, so the compiler waits for them here and not at their
+// first uses inside the store loop -- where, the loads sitting in branches, it could only
+// write vmcnt(0), behind the previous item's record store.
+template <int SK>
+__device__ __forceinline__ void os_loads_in(const int64_t (&v0)[SK], const int64_t (&v1)[SK], const uint32_t (&nx)[SK]) {
+#pragma unroll
+  for (int k = 0; k < SK; ++k) asm volatile("" ::"v"(v0[k]), "v"(v1[k]), "v"(nx[k]));
 }
 
 // A tile's ranks (below kST), two to a word: what the persistent sort carries to the store phase.
@@ -659,9 +702,22 @@ __global__ __launch_bounds__(kST) void mbx_onesweep_kernel(SortIn in, MboxView m
 // column: tile i+1's actor loads are issued before tile i's record stores, it is resolved
 // and ranked right after them, and its runs' reservations (one returning atomic per shard)
 // come back behind tile i+1's argument loads.  Only the next tile's actors / mailboxes and
-// packed ranks (12 registers) cross an iteration; the arguments are never loaded a tile
-// ahead (the 208-VGPR form, profiles/r5_mailbox_ab.md).  The prefixes and wave offsets are
-// double-buffered in LDS, so a tile costs two barriers.
+// packed ranks (12 registers) cross an iteration whole; the arguments are never held a tile
+// ahead of their stores (the 208-VGPR form, profiles/r5_mailbox_ab.md).  The prefixes, the
+// wave offsets and the spill vote's flag word are double-buffered in LDS, so a tile costs
+// two barriers: one between its votes / prefixes and its stores, one between the next
+// tile's ranking and its reservations.
+//
+// What is in flight where (profiles/sort_drain_waits.md).  Tile i+1's 16 argument loads are
+// issued directly behind tile i's last record store -- the registers are dead there -- and
+// cross tile i+1's resolve, ranking, barrier and reservation, none of which waits for
+// memory (the actors came in with tile i's arguments).  A whole tile's argument loads carry
+// no bounds branches (load_args_tile).  At the top of iteration i+1 tile i+2's actor loads
+// go out behind them; then ONE wait takes in all of them (os_loads_in), on every path, ahead
+// of the barrier: from there to the tile's last record store no instruction waits on vmcnt,
+// so the stores -- which count in vmcnt on gfx950 -- issue back to back.  The vote is a flag
+// word a wave sets before the first barrier when a lane spills, read behind it, cleared
+// behind the second (in place of __syncthreads_or: three barriers around an LDS word).
 //
 // Tiles: no counter, no flag, no block waits for another.  Block b of G (a multiple of 8
 // where there are 8 or more) sits on XCD b % 8; with a tile count that is a multiple of 8
@@ -686,6 +742,7 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
   uint32_t* wcnt2 = pre2 + 2 * S;                                             // [2][kST / kWave][S]
   uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_ps + ((persist_lds_bytes(S) + 15) & ~(size_t)15));
   __shared__ uint32_t tmax[3];
+  __shared__ uint32_t vote[2];  // the spill vote's flag word of a tile, double-buffered like pre / wcnt
   const unsigned w = threadIdx.x / kWave, lane = lane_id();
   // this block's tiles: first, first + stride, ... (n of them)
   const uint32_t G = gridDim.x, T = in.tiles;
@@ -705,18 +762,22 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
     base[s] = tl;
   }
   if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
+  if (threadIdx.x < 2) vote[threadIdx.x] = 0;
   for (uint32_t s = lane; s < S; s += kWave) wcnt2[w * S + s] = 0;
   __syncthreads();
   const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
   const bool maxima = in.rec8 || in.recw;
   uint32_t n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;  // (a block's share of a batch: below 2^32)
-  // the first tile, up to its reservations in flight
+  // the first tile, up to its reservations in flight; its arguments behind its actors
   uint32_t nx[SK];  // the coming tile: actors, then mailboxes
+  int64_t v0[SK], v1[SK];  // the coming tile's arguments, in flight from behind the last tile's stores
   PackedRanks<SK> wrp;
   {
     uint32_t a[SK], wr[SK];
     int r[SK];
+    const bool full = tile_is_full<SK>(in, first);
     load_actors<SK>(in, first, a);
+    load_args_tile<SK>(in, first, full, v0, v1);
     os_resolve<4, SK>(in, lpres, a, r, nx);
     os_rank<SK>(in, mv.log_s, first, r, nx, wcnt2 + w * S, wr);
 #pragma unroll
@@ -733,15 +794,19 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
     const uint32_t t = first + it * stride, b = it & 1;
     uint32_t* pre = pre2 + b * S;
     uint32_t* wcnt_all = wcnt2 + b * (kST / kWave) * S;
-    uint32_t mb[SK], meth[SK];
-    int64_t v0[SK], v1[SK], v2[SK];
+    const bool full = tile_is_full<SK>(in, t);
+    uint32_t mb[SK];
 #pragma unroll
     for (int k = 0; k < SK; ++k) mb[k] = nx[k];
-    // the tile's arguments, then the next tile's actors (in flight across this tile's stores); the tile's
-    // reservations, issued a tile ago, return behind them
-    load_cols<false, false, SK>(in, t, v0, v1, v2, meth);
+    // the next tile's actors (in flight across this tile's stores), behind this tile's arguments and its
+    // reservations, both issued a tile ago
     const bool more = it + 1 < n;
+    const bool full_next = more && tile_is_full<SK>(in, t + stride);
     if (more) load_actors<SK>(in, t + stride, nx);
+    // the one wait for the tile's loads, on every path: nothing below, up to the last record store, waits
+    // for memory again -- not for the run words' stores either (the next tile's actors are in with the
+    // arguments: its ranking follows the stores)
+    os_loads_in<SK>(v0, v1, nx);
     int sp = 0;
     if (threadIdx.x < S) {
       const uint32_t s = threadIdx.x;
@@ -750,7 +815,10 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
     }
     const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
     sp |= escm != 0;
-    const bool tile_spill = __syncthreads_or(sp) != 0;
+    // the spill vote: a wave with a spilling lane sets this tile's flag word, read behind the tile's barrier
+    if (__any(sp) && lane == 0) vote[b] = 1u;
+    __syncthreads();
+    const bool tile_spill = __builtin_amdgcn_readfirstlane((int)vote[b]) != 0;  // (block-uniform: a scalar)
     if (threadIdx.x == 0) {
       // (a tile spilled by its records' widths: flagged for the drains, as in onesweep_tile)
       if (tile_spill) tinfo[(size_t)t * 2 * S + S] |= kRunSpilled;
@@ -762,11 +830,14 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
 #pragma unroll
     for (int k = 0; k < SK; ++k) {
       const int64_t i = tile_index<SK>(t, k);
-      if (i >= in.M) continue;
-      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], v2[k], meth[k],
+      if (!full && i >= in.M) continue;
+      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], 0, in.method_uniform,
                        (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
     }
     if (more) {
+      // the next tile's arguments, right behind this tile's stores: in flight across its resolve, rank,
+      // barrier and reservation
+      load_args_tile<SK>(in, t + stride, full_next, v0, v1);
       // the next tile in the other buffer (last read before this tile's barrier): resolved, ranked, reserved
       uint32_t* wnext = wcnt2 + (b ^ 1) * (kST / kWave) * S;
       for (uint32_t s = lane; s < S; s += kWave) wnext[w * S + s] = 0;
@@ -779,6 +850,9 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
 #pragma unroll
       for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
       __syncthreads();
+      // (every thread has read this tile's flag word: cleared for the tile after the next, whose votes
+      // follow the next tile's barrier)
+      if (threadIdx.x == 0) vote[b] = 0u;
       if (threadIdx.x < S) {
         rc = os_wave_offsets(wnext, S, threadIdx.x);
         rx = os_reserve(mv, threadIdx.x, rc);
@@ -1165,14 +1239,31 @@ __device__ __forceinline__ DrainCounts drain_ring_tile(MboxView mv, SortIn in, u
     sst[local] = (uint8_t)rr.status;
     ++done;
   }
+  // Every record load is waited for here, on every path: a record is loaded under `j < T` and
+  // decoded under `sl[k] != kNoSlot`, so the compiler sees a path on which the load is still out
+  // when its registers are written again in the write-out below, and -- the outstanding count
+  // being unknown behind the branches -- put an s_waitcnt vmcnt(0) in front of each item, behind
+  // the previous item's reply stores (stores count in vmcnt on gfx950): a block's 8 store pairs
+  // went out one acknowledged round trip after another (profiles/sort_drain_waits.md).
+  __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
   __syncthreads();
+  // the tile's replies, coalesced (misses were answered by the scatter): the staged pairs into
+  // registers first, then the stores of the present ones back to back
   // (non-temporal: 56.4-58.8 vs 54.1-55.7 G on the headline step, one box, alternated; the
   // same stores measured flat-to-slower in the arrival, SeqFold and N > 1 completions,
   // which keep plain stores -- profiles/r6_small_sends.md)
+  uint8_t rst[SK];
+  int64_t rval[SK];
 #pragma unroll
-  for (int k = 0; k < SK; ++k) {  // the tile's replies, coalesced (misses were answered by the scatter)
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t j = (uint32_t)k * kST + threadIdx.x;  // (below kST * SK: inside both stages)
+    rst[k] = j < n_t ? sst[j] : kAbsent;
+    rval[k] = sval[j];
+  }
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
     const uint32_t j = (uint32_t)k * kST + threadIdx.x;
-    if (j < n_t && sst[j] != kAbsent) put_reply_nt(rv, in.origin_base + (uint32_t)(i0 + j), sval[j], sst[j]);
+    if (rst[k] != kAbsent) put_reply_nt(rv, in.origin_base + (uint32_t)(i0 + j), rval[k], rst[k]);
   }
   return DrainCounts{done, failed, holes};
 }
