@@ -49,6 +49,25 @@ Roctx& roctx() {
 }
 }  // namespace
 
+namespace {
+// A sorted mailbox Send's plan (mailbox_plan.hpp) as a dict; `kernels`: the variants its keys select
+py::dict plan_dict(const ptype::SortPlan& p) {
+  py::dict d;
+  d["tiles"] = p.tiles, d["G"] = p.G, d["tpb"] = p.tpb, d["tile_grid"] = p.tile_grid, d["ngroups"] = p.ngroups;
+  d["sort_mode"] = p.sort_mode, d["mode"] = p.mode, d["route"] = p.route;
+  d["view_shards"] = p.view_shards, d["view_shift"] = p.view_shift;
+  d["arrival"] = p.arrival, d["reserve"] = p.reserve, d["msg_drain"] = p.msg_drain, d["all_sidx"] = p.all_sidx;
+  d["rank_route"] = p.rank_route, d["pres_route"] = p.pres_route, d["persist"] = p.persist, d["fused"] = p.fused;
+  d["r8"] = p.r8, d["r8_on"] = p.r8_on, d["rw_on"] = p.rw_on, d["rf"] = p.rf, d["rec_bytes"] = p.rec_bytes;
+  d["ord_a12"] = p.ord_a12, d["arr_fused"] = p.arr_fused, d["rank_arr"] = p.rank_arr, d["pres_arr"] = p.pres_arr;
+  d["allow8"] = p.allow8, d["small_tiles"] = p.small_tiles, d["arr_tiles"] = p.arr_tiles, d["arr_grid"] = p.arr_grid;
+  d["sort_cap"] = p.sort_cap, d["need_stage_rep"] = p.need_stage_rep, d["need_r8esc"] = p.need_r8esc;
+  d["need_pres"] = p.need_pres, d["build_pres"] = p.build_pres;
+  d["kernels"] = ptype::mailbox_plan_kernels(p);
+  return d;
+}
+}  // namespace
+
 namespace ptype {
 void launch_table_upsert(uintptr_t, uint64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t,
                          uintptr_t, uintptr_t);
@@ -245,6 +264,41 @@ PYBIND11_MODULE(_hip, m) {
     d["poll_full"] = t.poll_full, d["poll_sleep"] = t.poll_sleep;
     return d;
   }, "the native path switches in force");
+  m.def("mailbox_variants", &mailbox_variant_names,
+        "every kernel a sorted mailbox Send can launch: the rows of the variant tables (csrc/hip/mailbox_sort*.hip)");
+  m.def(
+      "mailbox_send_plan",
+      [](int64_t M, uint32_t shards, uint32_t slots, bool planar, bool with_a2, const std::string& tune_spec,
+         bool widths_overflowed, bool consumer_running, uintptr_t actor, uintptr_t a0, uintptr_t a1, uintptr_t a2,
+         uintptr_t method_col, int method_uniform, uint64_t cap, uintptr_t dir, uint32_t n_dir, uint32_t affine_w,
+         int rank_self, uint32_t origin_base, uintptr_t out_val, uintptr_t out_st, uint64_t out_n, uint32_t n_state,
+         const std::vector<uintptr_t>& outbox, uint64_t outbox_cap, bool arrival, bool ordered, int fixed_method,
+         int sort_mode, uintptr_t dir_rank, uintptr_t pres, int pres_rank) -> py::object {
+        if (!shards || (shards & (shards - 1)) || !slots || (slots & (slots - 1)))
+          throw std::invalid_argument("mailbox_send_plan: shards and slots are powers of two");
+        MboxSend a;
+        a.actor = actor, a.a0 = a0, a.a1 = a1, a.a2 = a2, a.method_col = method_col;
+        a.method_uniform = method_uniform, a.M = M, a.cap = cap, a.dir = dir, a.n_dir = n_dir, a.affine_w = affine_w;
+        a.rank_self = rank_self, a.origin_base = origin_base, a.out_val = out_val, a.out_st = out_st, a.out_n = out_n;
+        a.n_state = n_state, a.outbox = outbox, a.outbox_cap = outbox_cap, a.arrival = arrival, a.ordered = ordered;
+        a.fixed_method = fixed_method, a.sort_mode = sort_mode, a.dir_rank = dir_rank, a.pres = pres;
+        a.pres_rank = pres_rank;
+        const RingGeom g{(uint32_t)__builtin_ctz(shards), (uint32_t)__builtin_ctz(slots), planar, with_a2};
+        if (!validate_sorted(a, g, consumer_running)) return py::none();
+        return plan_dict(plan_sorted(a, Tune::parse(tune_spec), g, widths_overflowed));
+      },
+      py::arg("M"), py::arg("shards") = 256, py::arg("slots") = 65536, py::arg("planar") = true,
+      py::arg("with_a2") = true, py::arg("tune") = "", py::arg("widths_overflowed") = false,
+      py::arg("consumer_running") = false, py::arg("actor") = 1, py::arg("a0") = 1, py::arg("a1") = 0,
+      py::arg("a2") = 0, py::arg("method_col") = 0, py::arg("method_uniform") = 0, py::arg("cap") = 1024,
+      py::arg("dir") = 0, py::arg("n_dir") = 0, py::arg("affine_w") = 0, py::arg("rank_self") = 0,
+      py::arg("origin_base") = 0, py::arg("out_val") = 1, py::arg("out_st") = 1, py::arg("out_n") = 0x7fffffffull,
+      py::arg("n_state") = 0, py::arg("outbox") = std::vector<uintptr_t>{}, py::arg("outbox_cap") = 0,
+      py::arg("arrival") = false, py::arg("ordered") = true, py::arg("fixed_method") = 0, py::arg("sort_mode") = 0,
+      py::arg("dir_rank") = 0, py::arg("pres") = 0, py::arg("pres_rank") = -1,
+      "what Mailboxes.send_sorted would do with these arguments on rings of this geometry, under the tune "
+      "switches `tune` alone ('key=value,...'): host code, no GPU.  Columns and tables are given as "
+      "addresses (nonzero: present).  None for an empty batch; raises what the Send would raise");
   m.def("set_route_tuning", &set_route_tuning, py::arg("prep_items") = 0, py::arg("mode") = 0,
         py::arg("prep_pipe") = 0,
         "3-pass route_prep items per thread (1, 2, 4, 8; 0 = default); mode 0 = 3-pass prep/scan/scatter "
@@ -642,6 +696,8 @@ PYBIND11_MODULE(_hip, m) {
       .def_property_readonly("last_record_bytes", &Mailboxes::last_record_bytes)
       .def_property_readonly("last_view_shards", &Mailboxes::last_view_shards)
       .def_property_readonly("last_route", &Mailboxes::last_route)
+      .def_property_readonly("last_plan", [](const Mailboxes& mb) { return plan_dict(mb.last_plan()); },
+                             "the last sorted Send's plan (mailbox_send_plan's dict)")
       .def_property_readonly("next_record_widths", &Mailboxes::next_record_widths)
       .def_property_readonly("consumer_processed", &Mailboxes::consumer_processed)
       .def_property_readonly("launches", &Mailboxes::launches)

@@ -48,17 +48,13 @@
 
 #include "common.hpp"
 #include "handlers.hpp"
+#include "mailbox_plan.hpp"
 
 namespace ptype {
 
 constexpr int kMboxCtrStride = 32;  // u64 words per shard: [0] tail, [1] done (one line), [16] head (another)
 constexpr int kMboxCtrTicket = 24;  // [24]: the epoch drain's per-shard last-block ticket (self-resetting)
 constexpr int kMboxMaxShards = 4096;
-// Sorted epoch mailboxes (mailbox_sort.hip): shard limit, and the per-(block,
-// shard) histogram's size -- it bounds the count / scatter grid (G <= words / S)
-constexpr int kMboxSortMaxShards = 1024;
-constexpr uint32_t kMboxSortHistWords = 1u << 18;
-constexpr uint32_t kMboxSortGroups = 32;  // group sums of 32 blocks each (G <= 1024)
 enum MboxStat : int {
   kMbEnqueued = 0,   // records written into rings
   kMbOverflow = 1,   // messages answered kStatusOverflow (ring full)
@@ -130,45 +126,26 @@ void launch_mailbox_consumer(const MboxView& mv, MboxCtrl* ctrl, uintptr_t state
                              uint64_t delay_ticks, const ReplyView& rv, int blocks, uint64_t idle_ticks,
                              uint64_t max_ticks, uintptr_t stream);
 
-// One epoch Send through the sorted mailboxes (Mailboxes::send_sorted).
-struct MboxSend {
-  uintptr_t actor = 0, a0 = 0, a1 = 0, a2 = 0, method_col = 0;
-  int method_uniform = 0;
-  int64_t M = 0;
-  uintptr_t table = 0;
-  uint64_t cap = 0;
-  uintptr_t dir = 0;
-  uint32_t n_dir = 0, affine_w = 0;
-  int rank_self = 0;
-  uint32_t origin_base = 0;
-  uintptr_t out_val = 0, out_st = 0;
-  uint64_t out_n = 0;
-  uintptr_t state = 0;
-  uint32_t n_state = 0;
-  uint64_t delay_ticks = 0;
-  std::vector<uintptr_t> outbox;
-  uint64_t outbox_cap = 0;
-  bool arrival = false;  // shard by arrival tile (batches without ordered methods)
-  bool ordered = true;   // ordered drain: per-actor serial, FIFO; else the parallel drain
-  int fixed_method = 0;  // every message carries this method (constant-folded handler)
-  // sort kernels: 0 auto (tune mbox_sort, else one-pass for stateless batches and from 1024
-  // tiles on), 1 one-pass (stateless: run reservations; ordered: look-back), 2 count + scatter
-  int sort_mode = 0;
-  uintptr_t stream = 0;
-  // the directory's rank byte table (one byte per id): a stateless uniform batch
-  // resolves only its rank (1 MB at 1 M ids, L2-resident, against the 4 MB
-  // directory) and its records carry the actor id, which no stateless handler reads
-  uintptr_t dir_rank = 0;
-  // route mode 4's presence map of the directory, kept by the registry mirror for
-  // rank pres_rank (rebuilt with the directory; RegistryTable.presence): used when it is
-  // this Send's rank, else the Send folds its own from dir_rank
-  uintptr_t pres = 0;
-  int pres_rank = -1;
-};
-
 // Route mode 4's presence map: 2 bits per directory id for rank `rank` (mailbox_sort.hip)
 uint32_t presence_words(uint32_t n_dir);
 void launch_presence(uintptr_t dir_rank, uint32_t n_dir, int rank, uintptr_t out, uintptr_t stream);
+
+// The kernels a sorted Send can launch, as the variant tables list them (mailbox_sort*.hip),
+// and the ones a plan's keys select; a key that selects no row, or two, throws
+std::vector<std::string> mailbox_variant_names();
+std::vector<std::string> mailbox_plan_kernels(const SortPlan& p);
+
+// send_sorted's workspaces as its launchers take them (Mailboxes::sort_ws; the members say what each holds)
+struct SortWs {
+  uint32_t *hist, *gsum;
+  unsigned* ticket;
+  uint32_t *rw, *sidx, *tinfo;
+  unsigned long long* desc;
+  unsigned* tctr;
+  uint32_t *r8w, *r8max, *r8host;
+  int64_t* r8esc;
+  void* stage_rep;
+};
 
 class Mailboxes {
  public:
@@ -209,12 +186,15 @@ class Mailboxes {
   uint32_t shards() const { return 1u << mv_.log_s; }
   uint32_t slots() const { return 1u << mv_.log_q; }
   uint64_t bytes() const { return bytes_; }
-  // ring record bytes of the last sorted Send (8: 8-B records, 16: compact, 32: long records in use)
-  int last_record_bytes() const { return last_rec_bytes_; }
-  // shards the last sorted Send's rings were viewed as (stateless batches: a coarser view, 8 by default)
-  uint32_t last_view_shards() const { return last_view_shards_; }
-  // the last sorted Send's route: 0 hash probe, 1 directory, 2 affine rule, 3 rank byte table
-  int last_route() const { return last_route_; }
+  // what the last sorted Send did (mailbox_plan.hpp), and what plan_sorted needs of the rings
+  const SortPlan& last_plan() const { return last_plan_; }
+  RingGeom geometry() const { return RingGeom{mv_.log_s, mv_.log_q, mv_.planar != 0, mv_.a2 != nullptr}; }
+  // its ring record bytes (8: 8-B records, 18: wide pure, 16: compact, 32: long records in use)
+  int last_record_bytes() const { return last_plan_.rec_bytes; }
+  // shards its rings were viewed as (stateless batches: a coarser view, 8 by default)
+  uint32_t last_view_shards() const { return last_plan_.view_shards; }
+  // its route: 0 hash probe, 1 directory, 2 affine rule, 3 rank byte table, 4 presence map
+  int last_route() const { return last_plan_.route; }
   // the 8-B field widths the next 8-B Send will run on, as the device left them in the
   // pinned mirror: wm | w0 << 8 | w1 << 16, bit 31 = the fields outgrew 8 B.  -1 before
   // the first 8-B Send; current once the stream of the last Send is synchronised.
@@ -242,13 +222,15 @@ class Mailboxes {
   unsigned long long* sort_desc_ = nullptr;  // [tiles][S] one-pass sort: per-tile shard counts / prefixes (look-back)
   unsigned* sort_tctr_ = nullptr;   // [0] one-pass sort's tile counter (self-resetting), [1] its epoch tag
   uint64_t sort_cap_ = 0;           // messages the two arrays hold
-  int last_rec_bytes_ = 0;
-  uint32_t last_view_shards_ = 0;
-  int last_route_ = -1;
+  SortPlan last_plan_;
   uint32_t* sort_resv_ = nullptr;   // [S][kResvStride] one-pass run reservations (zero between Sends)
   uint32_t* pres_ = nullptr;        // route mode 4: 2-bit presence map of the route directory (per Send)
-  const uint32_t* pres_view_ = nullptr;  // the map this Send reads (pres_, or the registry mirror's)
-  void build_presence(const MboxSend& a, hipStream_t st);
+  const uint32_t* build_presence(const MboxSend& a, hipStream_t st);
+  // send_sorted's workspaces (grown or first allocated outside graph capture)
+  bool grow_workspaces(const SortPlan& p, const MboxSend& a, hipStream_t st);
+  void first_use_workspaces(const SortPlan& p, hipStream_t st);
+  bool widths_overflowed() const { return r8host_ && (__atomic_load_n(r8host_, __ATOMIC_RELAXED) & 0x80000000u); }
+  SortWs sort_ws() const;
   uint64_t pres_words_ = 0;
   // 8-B ring records: [0] the field widths in force (device; updated by each Send's
   // last block), per-tile field bit lengths, and a pinned mirror of [0] (bit 31: the

@@ -63,35 +63,457 @@
 
 namespace ptype {
 
-static bool fused_ok(int64_t tiles) {
-  const int f = tune().mbox_fused;
-  return f == 1 || (f < 0 && tiles <= 512);
-}
-
-// The persistent presence-map sort (tune mbox_persist): auto takes it for batches past 512
-// tiles, where every resident block has more than one tile to walk.
-static bool persist_ok(int64_t tiles) {
-  const int p = tune().mbox_persist;
-  return p == 1 || (p < 0 && tiles > 512);
-}
-
-// Its grid: the blocks the device keeps resident at this LDS size, at most one per tile,
-// a multiple of 8 from 8 up (whole XCD rounds).  (The current device is the Send's.)
-static uint32_t persist_grid(size_t lds, int64_t tiles) {
-  thread_local int c_dev = -1, c_resident = 0;  // the last answer (a Send repeats its device and map size)
-  thread_local size_t c_lds = 0;
-  int dev = 0;
-  PT_HIP_CHECK(hipGetDevice(&dev));
-  if (dev != c_dev || lds != c_lds) {
-    int cus = 0, per_cu = 0;
-    PT_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    PT_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)mbx_persist_sort_kernel<>, kST, lds));
-    c_resident = std::max(per_cu, 1) * std::max(cus, 1);
-    c_dev = dev, c_lds = lds;
+// ---------------------------------------------------------------- K2s pass 1: count
+template <int MODE>
+__global__ __launch_bounds__(kST) void mbx_count_kernel(SortIn in, uint32_t log_s, uint32_t* __restrict__ hist,
+                                                        uint32_t* __restrict__ gsum, uint32_t* __restrict__ rw) {
+  __shared__ uint32_t cnt[kMboxSortMaxShards];
+  const uint32_t S = 1u << log_s;
+  const uint32_t v = virt_block(blockIdx.x, in.G);
+  for (uint32_t s = threadIdx.x; s < S; s += kST) cnt[s] = 0;
+  __syncthreads();
+  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
+  uint32_t a[kSK];
+  if (t0 < t1) load_actors(in, t0, a);
+  for (uint32_t t = t0; t < t1; ++t) {
+    int r[kSK];
+    uint32_t mb[kSK];
+    resolve_k<MODE>(in, a, r, mb);
+    if (t + 1 < t1) load_actors(in, t + 1, a);  // next tile's loads in flight while this one counts
+#pragma unroll
+    for (int k = 0; k < kSK; ++k) {
+      const int64_t i = tile_index(t, k);
+      const bool ok = r[k] == in.rank_self && mb[k] < kMaxMbox;
+      if (i < in.M) rw[i] = ok ? mb[k] : kNoSlot;
+      if (ok) atomicAdd(&cnt[mb[k] & (S - 1)], 1u);
+    }
   }
-  int64_t g = std::min<int64_t>(c_resident, tiles);
-  if (g >= 8) g -= g % 8;
-  return (uint32_t)g;
+  __syncthreads();
+  uint32_t* g = gsum + (size_t)(v / kGroupBlocks) * S;
+  for (uint32_t s = threadIdx.x; s < S; s += kST) {
+    const uint32_t c = cnt[s];
+    hist[(size_t)v * S + s] = c;
+    if (c) atomicAdd(&g[s], c);
+  }
+}
+
+// ---------------------------------------------------------------- K2s pass 2: scatter
+// The tile's arguments are loaded with its route words, before the ranking (in
+// flight across it).  Loading them only once the ranks are known (a smaller
+// register file, occupancy 4 -> 5) measured slower: 124 -> 164 us per 8 Mi.
+template <bool A2, bool MC>
+__device__ __forceinline__ void load_routed(const SortIn& in, const uint32_t* __restrict__ rw, uint32_t t,
+                                            uint32_t (&m)[kSK], int64_t (&x0)[kSK], int64_t (&x1)[kSK],
+                                            int64_t (&x2)[kSK], uint32_t (&meth)[kSK]) {
+#pragma unroll
+  for (int k = 0; k < kSK; ++k) {
+    const int64_t i = tile_index(t, k);
+    const bool ok = i < in.M;
+    m[k] = ok ? __builtin_nontemporal_load(rw + i) : kNoSlot;
+    x0[k] = ok ? __builtin_nontemporal_load(in.a0 + i) : 0;
+    x1[k] = ok && in.a1 ? __builtin_nontemporal_load(in.a1 + i) : 0;
+    x2[k] = 0;
+    if constexpr (A2) x2[k] = ok ? __builtin_nontemporal_load(in.a2 + i) : 0;
+    meth[k] = in.method_uniform;
+    if constexpr (MC) meth[k] = ok ? (uint32_t)in.mcol[i] : 0u;
+  }
+}
+
+// Per-tile runs (`tinfo`, [tiles][2][S] u32): tile t's records of shard s sit at
+// ring slots s | ((bias + j) & (Q - 1)), j < count (bias = epoch-start tail +
+// the run's offset + the shard's rotation; count clamped to the free room, its
+// top bit set when the run spilled / overflowed the room) -- what the ring-order
+// drain and completion read instead of a per-message slot index.  The slot
+// index `sidx` is written only where a consumer needs it: every message with
+// `all_sidx` (the message-order drain, tune mbox_drain_msg=1), and the whole
+// tile when some message of it spilled (the drain runs that tile in message
+// order).  (An opt-in LDS-staged write-out in ring order measured slower,
+// 117 -> 161 us per 8 Mi msgs: the 80 KB stage halved the resident blocks;
+// removed, see git history 4c4ea76.)
+__host__ __device__ constexpr size_t scatter_lds_bytes(uint32_t S) { return (size_t)S * (16 + 4 * (kST / kWave)); }
+
+template <bool A2, bool MC>
+__global__ __launch_bounds__(kST) void mbx_scatter_kernel(SortIn in, MboxView mv, const uint32_t* __restrict__ hist,
+                                                          const uint32_t* __restrict__ gsum,
+                                                          uint32_t* __restrict__ rw,
+                                                          uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
+                                                          ReplyView rv, bool spill, bool all_sidx) {
+  // LDS sized by the shard count (16 + 4 * waves B per shard): occupancy is not
+  // capped by the 1024-shard maximum
+  extern __shared__ __align__(16) unsigned char smem_sc[];
+  const uint32_t S = 1u << mv.log_s;
+  unsigned long long* base = reinterpret_cast<unsigned long long*>(smem_sc);  // ring position of offset 0 (tail)
+  uint32_t* run = reinterpret_cast<uint32_t*>(base + S);  // this block's next offset per shard
+  uint32_t* room = run + S;                               // offset limit (free ring slots)
+  uint32_t* wcnt_all = room + S;                          // [kST / kWave][S] per-wave counts -> wave offsets
+  auto wcnt = [&](unsigned ww, uint32_t sh) -> uint32_t& { return wcnt_all[ww * S + sh]; };
+  const uint64_t Q = 1ull << mv.log_q;
+  const uint32_t v = virt_block(blockIdx.x, in.G);
+  const unsigned w = threadIdx.x / kWave, lane = lane_id();
+  const uint32_t g0 = v / kGroupBlocks, v0 = g0 * kGroupBlocks;
+  for (uint32_t s = threadIdx.x; s < S; s += kST) {
+    // this block's prefix: whole groups before it, then the rows before it in its group
+    uint32_t p = 0;
+    for (uint32_t g = 0; g < g0; ++g) p += gsum[(size_t)g * S + s];
+    for (uint32_t u = v0; u < v; ++u) p += hist[(size_t)u * S + s];
+    run[s] = p;
+    const uint64_t tl = *ctr_tail(mv, s), hd = *ctr_head(mv, s);
+    base[s] = tl;
+    const uint64_t free = hd + Q > tl ? hd + Q - tl : 0;
+    room[s] = (uint32_t)(free < 0xffffffffull ? free : 0xffffffffull);
+  }
+  unsigned long long n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;
+  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
+  for (uint32_t t = t0; t < t1; ++t) {
+    for (uint32_t s = lane; s < S; s += kWave) wcnt(w, s) = 0;  // this wave's row only
+    uint32_t mb[kSK], meth[kSK];
+    int64_t v0[kSK], v1[kSK], v2[kSK];
+    load_routed<A2, MC>(in, rw, t, mb, v0, v1, v2, meth);
+    // rank of each message among this wave's earlier messages of its shard
+    uint32_t wr[kSK], sh[kSK];
+#pragma unroll
+    for (int k = 0; k < kSK; ++k) {
+      const bool ok = mb[k] != kNoSlot;
+      sh[k] = mb[k] & (S - 1);
+      const uint64_t peers = match_bits(sh[k], mv.log_s, __ballot(ok));
+      const unsigned below = mbcnt64(peers);
+      const int leader = peers ? __builtin_ctzll(peers) : 0;
+      unsigned old = 0;
+      if (ok && below == 0) {  // group leader: one plain LDS read-add per distinct shard of the wave
+        old = wcnt(w, sh[k]);
+        wcnt(w, sh[k]) = old + (unsigned)__popcll(peers);
+      }
+      wr[k] = (unsigned)__shfl((int)old, leader) + below;
+    }
+    __syncthreads();
+    int sp = 0;
+    for (uint32_t s = threadIdx.x; s < S; s += kST) {  // wave offsets in message order, then the block's run
+      uint32_t rr = run[s];
+#pragma unroll
+      for (int ww = 0; ww < kST / kWave; ++ww) {
+        const uint32_t c = wcnt(ww, s);
+        wcnt(ww, s) = rr;
+        rr += c;
+      }
+      run[s] = rr;
+      sp |= rr > room[s];
+    }
+    bool tile_spill = false;  // (either barrier publishes the wave offsets too)
+    if (spill) tile_spill = __syncthreads_or(sp) != 0;
+    else __syncthreads();
+    const bool wsidx = all_sidx || tile_spill;
+#pragma unroll
+    for (int k = 0; k < kSK; ++k) {
+      const int64_t i = tile_index(t, k);
+      if (i >= in.M) continue;
+      const uint32_t origin = in.origin_base + (uint32_t)i;
+      if (mb[k] == kNoSlot) {
+        ++n_miss;
+        if (wsidx) sidx[i] = kNoSlot;
+        write_status(rv, origin, kStatusNoActor);
+        continue;
+      }
+      const uint32_t off = wcnt(w, sh[k]) + wr[k];
+      if (off >= room[sh[k]]) {  // the ring is full
+        if (spill) {  // stateless batch: the drain runs it from the batch
+          ++n_spill;
+          sidx[i] = kSpillSlot;
+          continue;
+        }
+        ++n_ovf;  // answered now, re-sent by send_all
+        if (wsidx) sidx[i] = kNoSlot;
+        write_status(rv, origin, kStatusOverflow);
+        continue;
+      }
+      const int64_t x0 = v0[k], x1 = v1[k], x2 = v2[k];
+      const uint32_t mt = meth[k];
+      const uint64_t slot = slot_at(mv, sh[k], base[sh[k]] + off);
+      if (wsidx) sidx[i] = (uint32_t)slot;
+      if (mt < 128u && fits_i32(x0) && fits_i32(x1) && x2 == 0) {
+        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
+            u32x4{origin | kCompactMark, mb[k] | (mt << 24), (uint32_t)x0, (uint32_t)x1};
+      } else {
+        const uint32_t fl = x2 != 0 ? (uint32_t)kFlagA2 : 0u;
+        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
+            u32x4{origin | kCompactMark, mb[k] | kCompactLong, (mt & 0xffffu) | (fl << 16), 0u};
+        *reinterpret_cast<u32x4*>(rec_b(mv, slot)) =
+            u32x4{(uint32_t)x0, (uint32_t)((uint64_t)x0 >> 32), (uint32_t)x1, (uint32_t)((uint64_t)x1 >> 32)};
+        if (fl) mv.a2[slot] = x2;
+      }
+      ++n_enq;
+    }
+    if (tinfo) {  // the tile's runs (after the stores: the messages' registers are dead by now -- +25 VGPRs above)
+      // slot bias from the epoch-start tail (a drain may commit before the completion reads it)
+      for (uint32_t s = threadIdx.x; s < S; s += kST) {
+        const uint32_t r0 = wcnt(0, s), rr = run[s];  // wave 0's offset = the run before this tile
+        const uint32_t cc = r0 >= room[s] ? 0u : min(rr - r0, room[s] - r0);
+        tinfo[(size_t)t * 2 * S + s] = (uint32_t)(base[s] + r0) + shard_rot(mv, s);
+        tinfo[(size_t)t * 2 * S + S + s] = cc | (rr > room[s] ? kRunSpilled : 0u);
+      }
+    }
+    __syncthreads();  // wcnt rows are reused by the next tile
+  }
+  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_ovf, kMbOverflow, n_miss, kMbNoActor);
+  if (spill) {
+    __syncthreads();  // block_add_stats' LDS partials are reused
+    block_add_stats(mv.stats, n_spill, kMbSpilled, 0, -1, 0, -1);
+  }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(256) void mbx_presence_kernel(const uint8_t* __restrict__ dirr, uint32_t n_dir,
+                                                           int rank_self, uint32_t* __restrict__ pres) {
+  const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
+  if (wi >= pres_words(n_dir)) return;
+  alignas(16) uint8_t b[16];
+  if (wi * 16 + 16 <= n_dir) {  // (the table is a whole allocation: 16-B aligned)
+    *reinterpret_cast<uint4*>(b) = *reinterpret_cast<const uint4*>(dirr + (size_t)wi * 16);
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) b[j] = wi * 16 + j < n_dir ? dirr[wi * 16 + j] : kRankMissing;
+  }
+  uint32_t w = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) {
+    const uint32_t st = b[j] == (uint8_t)rank_self ? 1u : b[j] == kRankFallback ? 2u : 0u;
+    w |= st << (2 * j);
+  }
+  pres[wi] = w;
+}
+
+template <int MODE, bool A2, bool MC>
+__global__ __launch_bounds__(kST) void mbx_onesweep_kernel(SortIn in, MboxView mv, unsigned long long* __restrict__ desc,
+                                                           unsigned* __restrict__ tctr, uint32_t* __restrict__ gsum,
+                                                           uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
+                                                           uint32_t* __restrict__ rw, ReplyView rv, bool spill,
+                                                           bool all_sidx, bool reserve) {
+  extern __shared__ __align__(16) unsigned char smem_os[];
+  (void)onesweep_tile<MODE, A2, MC>(in, mv, desc, tctr, gsum, sidx, tinfo, rw, rv, spill, all_sidx, smem_os, reserve);
+}
+
+// ---------------------------------------------------------------- K2s persistent reserving sort
+// The reserving one-pass sort of a presence-map Send (route mode 4) as a grid of
+// resident blocks, each walking several tiles (tune mbox_persist).  What a tile of
+// mbx_onesweep_kernel<4> repeats and a Send needs once is done once per block: the map
+// staged in LDS, each ring's tail and room read, the enqueue counters added.  And the
+// tile's serial chain of round trips is shortened by running one tile ahead on the cheap
+// column: tile i+1's actor loads are issued before tile i's record stores, it is resolved
+// and ranked right after them, and its runs' reservations (one returning atomic per shard)
+// come back behind tile i+1's argument loads.  Only the next tile's actors / mailboxes and
+// packed ranks (12 registers) cross an iteration whole; the arguments are never held a tile
+// ahead of their stores (the 208-VGPR form, profiles/r5_mailbox_ab.md).  The prefixes, the
+// wave offsets and the spill vote's flag word are double-buffered in LDS, so a tile costs
+// two barriers: one between its votes / prefixes and its stores, one between the next
+// tile's ranking and its reservations.
+//
+// What is in flight where (profiles/sort_drain_waits.md).  Tile i+1's 16 argument loads are
+// issued directly behind tile i's last record store -- the registers are dead there -- and
+// cross tile i+1's resolve, ranking, barrier and reservation, none of which waits for
+// memory (the actors came in with tile i's arguments).  A whole tile's argument loads carry
+// no bounds branches (load_args_tile).  At the top of iteration i+1 tile i+2's actor loads
+// go out behind them; then ONE wait takes in all of them (os_loads_in), on every path, ahead
+// of the barrier: from there to the tile's last record store no instruction waits on vmcnt,
+// so the stores -- which count in vmcnt on gfx950 -- issue back to back.  The vote is a flag
+// word a wave sets before the first barrier when a lane spills, read behind it, cleared
+// behind the second (in place of __syncthreads_or: three barriers around an LDS word).
+//
+// Tiles: no counter, no flag, no block waits for another.  Block b of G (a multiple of 8
+// where there are 8 or more) sits on XCD b % 8; with a tile count that is a multiple of 8
+// it takes tiles x * T/8 + j, j = b / 8 + i * G/8 -- the XCD virt_block gives each tile in
+// the one-tile-per-block form, which is where the ring drain reads its runs.  Otherwise
+// tile b + i * G.  A tile's runs land in the rings in the order the blocks reserve them,
+// which a stateless ring allows (see onesweep_tile).
+__host__ __device__ constexpr size_t persist_lds_bytes(uint32_t S) {
+  return (size_t)S * (8 + 4 + 2 * 4 + 2 * 4 * (kST / kWave));
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx,
+                                                               uint32_t* __restrict__ tinfo, uint32_t* __restrict__ rw,
+                                                               ReplyView rv) {
+  constexpr int SK = kSK;
+  extern __shared__ __align__(16) unsigned char smem_ps[];
+  const uint32_t S = 1u << mv.log_s;
+  unsigned long long* base = reinterpret_cast<unsigned long long*>(smem_ps);  // each ring's epoch-start tail
+  uint32_t* room = reinterpret_cast<uint32_t*>(base + S);                     // offset limit past the tail
+  uint32_t* pre2 = room + S;                                                  // [2][S] a tile's prefix per shard
+  uint32_t* wcnt2 = pre2 + 2 * S;                                             // [2][kST / kWave][S]
+  uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_ps + ((persist_lds_bytes(S) + 15) & ~(size_t)15));
+  __shared__ uint32_t tmax[3];
+  __shared__ uint32_t vote[2];  // the spill vote's flag word of a tile, double-buffered like pre / wcnt
+  const unsigned w = threadIdx.x / kWave, lane = lane_id();
+  // this block's tiles: first, first + stride, ... (n of them)
+  const uint32_t G = gridDim.x, T = in.tiles;
+  uint32_t first = blockIdx.x, stride = G, n = blockIdx.x < T ? (T - blockIdx.x + G - 1) / G : 0u;
+  if (G >= 8 && (G & 7) == 0 && (T & 7) == 0) {
+    const uint32_t j = blockIdx.x >> 3, T8 = T >> 3;
+    stride = G >> 3;
+    first = (blockIdx.x & 7) * T8 + j;
+    n = j < T8 ? (T8 - j + stride - 1) / stride : 0u;
+  }
+  if (n == 0) return;
+  // once per block: the map, the rings' tails and room
+  stage_pres(in, lpres);
+  for (uint32_t s = threadIdx.x; s < S; s += kST) {
+    uint64_t tl;
+    room[s] = os_ring_room(mv, s, tl);
+    base[s] = tl;
+  }
+  if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
+  if (threadIdx.x < 2) vote[threadIdx.x] = 0;
+  for (uint32_t s = lane; s < S; s += kWave) wcnt2[w * S + s] = 0;
+  __syncthreads();
+  const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
+  const bool maxima = in.rec8 || in.recw;
+  uint32_t n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;  // (a block's share of a batch: below 2^32)
+  // the first tile, up to its reservations in flight; its arguments behind its actors
+  uint32_t nx[SK];  // the coming tile: actors, then mailboxes
+  int64_t v0[SK], v1[SK];  // the coming tile's arguments, in flight from behind the last tile's stores
+  PackedRanks<SK> wrp;
+  {
+    uint32_t a[SK], wr[SK];
+    int r[SK];
+    const bool full = tile_is_full<SK>(in, first);
+    load_actors<SK>(in, first, a);
+    load_args_tile<SK>(in, first, full, v0, v1);
+    os_resolve<4, SK>(in, lpres, a, r, nx);
+    os_rank<SK>(in, mv.log_s, first, r, nx, wcnt2 + w * S, wr);
+#pragma unroll
+    for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+  }
+  __syncthreads();
+  // (S <= kST: a shard's thread keeps its run's count and reserved offset in registers)
+  uint32_t rc = 0, rx = 0;
+  if (threadIdx.x < S) {
+    rc = os_wave_offsets(wcnt2, S, threadIdx.x);
+    rx = os_reserve(mv, threadIdx.x, rc);
+  }
+  for (uint32_t it = 0; it < n; ++it) {
+    const uint32_t t = first + it * stride, b = it & 1;
+    uint32_t* pre = pre2 + b * S;
+    uint32_t* wcnt_all = wcnt2 + b * (kST / kWave) * S;
+    const bool full = tile_is_full<SK>(in, t);
+    uint32_t mb[SK];
+#pragma unroll
+    for (int k = 0; k < SK; ++k) mb[k] = nx[k];
+    // the next tile's actors (in flight across this tile's stores), behind this tile's arguments and its
+    // reservations, both issued a tile ago
+    const bool more = it + 1 < n;
+    const bool full_next = more && tile_is_full<SK>(in, t + stride);
+    if (more) load_actors<SK>(in, t + stride, nx);
+    // the one wait for the tile's loads, on every path: nothing below, up to the last record store, waits
+    // for memory again -- not for the run words' stores either (the next tile's actors are in with the
+    // arguments: its ranking follows the stores)
+    os_loads_in<SK>(v0, v1, nx);
+    int sp = 0;
+    if (threadIdx.x < S) {
+      const uint32_t s = threadIdx.x;
+      pre[s] = rx;
+      sp = os_run_info(mv, tinfo, t, S, s, base[s], room[s], rx, rc);
+    }
+    const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
+    sp |= escm != 0;
+    // the spill vote: a wave with a spilling lane sets this tile's flag word, read behind the tile's barrier
+    if (__any(sp) && lane == 0) vote[b] = 1u;
+    __syncthreads();
+    const bool tile_spill = __builtin_amdgcn_readfirstlane((int)vote[b]) != 0;  // (block-uniform: a scalar)
+    if (threadIdx.x == 0) {
+      // (a tile spilled by its records' widths: flagged for the drains, as in onesweep_tile)
+      if (tile_spill) tinfo[(size_t)t * 2 * S + S] |= kRunSpilled;
+      if (maxima) {  // the tile's field bit lengths; cleared for the next tile (its maxima follow a barrier)
+        (void)atomicExch(&in.r8max[t], tmax[0] | (tmax[1] << 8) | (tmax[2] << 16));
+        tmax[0] = tmax[1] = tmax[2] = 0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SK; ++k) {
+      const int64_t i = tile_index<SK>(t, k);
+      if (!full && i >= in.M) continue;
+      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], 0, in.method_uniform,
+                       (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
+    }
+    if (more) {
+      // the next tile's arguments, right behind this tile's stores: in flight across its resolve, rank,
+      // barrier and reservation
+      load_args_tile<SK>(in, t + stride, full_next, v0, v1);
+      // the next tile in the other buffer (last read before this tile's barrier): resolved, ranked, reserved
+      uint32_t* wnext = wcnt2 + (b ^ 1) * (kST / kWave) * S;
+      for (uint32_t s = lane; s < S; s += kWave) wnext[w * S + s] = 0;
+      uint32_t a[SK], wr[SK];
+      int r[SK];
+#pragma unroll
+      for (int k = 0; k < SK; ++k) a[k] = nx[k];
+      os_resolve<4, SK>(in, lpres, a, r, nx);
+      os_rank<SK>(in, mv.log_s, t + stride, r, nx, wnext + w * S, wr);
+#pragma unroll
+      for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+      __syncthreads();
+      // (every thread has read this tile's flag word: cleared for the tile after the next, whose votes
+      // follow the next tile's barrier)
+      if (threadIdx.x == 0) vote[b] = 0u;
+      if (threadIdx.x < S) {
+        rc = os_wave_offsets(wnext, S, threadIdx.x);
+        rx = os_reserve(mv, threadIdx.x, rc);
+      }
+    }
+  }
+  // once per block: the enqueue counters
+  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_ovf, kMbOverflow, n_miss, kMbNoActor);
+  __syncthreads();  // block_add_stats' LDS partials are reused
+  block_add_stats(mv.stats, n_spill, kMbSpilled, 0, -1, 0, -1);
+}
+
+template <int FIXED>
+__global__ __launch_bounds__(kST) void mbx_drain_msg_kernel(MboxView mv, SortIn in, const uint32_t* __restrict__ sidx,
+                                                            const uint32_t* __restrict__ rw,
+                                                            int64_t* __restrict__ state, uint32_t n_state,
+                                                            uint64_t delay_ticks, OutboxView ob, ReplyView rv,
+                                                            uint32_t* __restrict__ gsum, uint32_t ngroups,
+                                                            unsigned* __restrict__ ticket, unsigned* __restrict__ tctr) {
+  // the scatter's block -> tile ranges: a tile's records sit in ~S short runs that
+  // this block's waves read whole (line reuse in L1 / L2), not one record per block
+  unsigned long long done = 0, failed = 0, holes = 0;
+  const uint32_t v = virt_block(blockIdx.x, in.G);
+  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
+  for (uint32_t t = t0; t < t1; ++t)
+    drain_tile_msg<FIXED>(mv, in, t, sidx, rw, state, n_state, delay_ticks, ob, rv, done, failed, holes);
+  block_add_stats(mv.stats, done, kMbProcessed, failed, kMbFailed, holes, kMbHoles);
+  __shared__ bool last;
+  if (threadIdx.x == 0) last = last_block_ticket(ticket);
+  __syncthreads();
+  if (last) {  // every block's records are read: the rings are consumed
+    const uint32_t S = 1u << mv.log_s;
+    for (uint32_t s = threadIdx.x; s < S; s += kST) epoch_commit(mv, s, epoch_sum(mv, gsum, ngroups, S, s));
+    if (threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag
+  }
+}
+
+template <int FIXED, bool NARROW, int RF, int SK = kSK>
+__global__ __launch_bounds__(kST, (NARROW && FIXED) ? 8 : 1) void mbx_drain_ring_kernel(MboxView mv, SortIn in, const uint32_t* __restrict__ tinfo,
+                                                             const uint32_t* __restrict__ sidx,
+                                                             const uint32_t* __restrict__ rw,
+                                                             int64_t* __restrict__ state, uint32_t n_state,
+                                                             uint64_t delay_ticks, OutboxView ob, ReplyView rv,
+                                                             uint32_t* __restrict__ gsum, uint32_t ngroups,
+                                                             unsigned* __restrict__ ticket, unsigned* __restrict__ tctr,
+                                                             uint32_t* __restrict__ r8host) {
+  extern __shared__ __align__(16) unsigned char smem_rd[];
+  const uint32_t S = 1u << mv.log_s;
+  DrainCounts dc;
+  // tiles dealt XCD by XCD like the scatter's blocks (whose writes the XCD's L2 may still hold)
+  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
+  if (t < in.tiles)
+    dc = drain_ring_tile<FIXED, NARROW, false, RF, SK>(mv, in, t, tinfo, sidx, rw, state, n_state, delay_ticks, ob,
+                                                       rv, smem_rd);
+  block_add_stats(mv.stats, dc.done, kMbProcessed, dc.failed, kMbFailed, dc.holes, kMbHoles);
+  __shared__ bool last;
+  if (threadIdx.x == 0) last = last_block_ticket(ticket);
+  __syncthreads();
+  if (last) {  // every block's records are read: the rings are consumed
+    for (uint32_t s = threadIdx.x; s < S; s += kST) epoch_commit(mv, s, epoch_sum(mv, gsum, ngroups, S, s));
+    if (threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag
+    if constexpr (RF != 0) rec8_next(in, const_cast<uint32_t*>(in.r8w), r8host, in.tiles);
+  }
 }
 
 // Removed variants (measured slower or flat; A/B rows in profiles/r4_mailbox_ab.md and
@@ -107,6 +529,108 @@ static uint32_t persist_grid(size_t lds, int64_t tiles) {
 // drain (233 vs 175 us), 2048-record ordered windows, the ordered drain without the
 // register fold or the prefetched window, 16-B ordered records at 8 Mi, the wide ring
 // drain and the 8 / 16 / 32-shard stateless views other than 8.
+
+// ---------------------------------------------------------------- variant tables (keys: mailbox_plan.hpp)
+static const Variant<decltype(mbx_count_kernel<0>)> kCount[] = {
+    MBX_ROW(vkey(0), 0, mbx_count_kernel<0>),
+    MBX_ROW(vkey(1), 0, mbx_count_kernel<1>),
+    MBX_ROW(vkey(2), 0, mbx_count_kernel<2>),
+};
+static const Variant<decltype(mbx_scatter_kernel<false, false>)> kScatter[] = {
+    MBX_ROW(vkey(0, 0), 0, mbx_scatter_kernel<false, false>),
+    MBX_ROW(vkey(0, 1), 0, mbx_scatter_kernel<false, true>),
+    MBX_ROW(vkey(1, 0), 0, mbx_scatter_kernel<true, false>),
+    MBX_ROW(vkey(1, 1), 0, mbx_scatter_kernel<true, true>),
+};
+// (routes 3 and 4: uniform stateless batches of at most two arguments)
+static const Variant<decltype(mbx_onesweep_kernel<0, false, false>)> kOnesweep[] = {
+    MBX_ROW(vkey(0, 0, 0), 0, mbx_onesweep_kernel<0, false, false>),
+    MBX_ROW(vkey(0, 0, 1), 0, mbx_onesweep_kernel<0, false, true>),
+    MBX_ROW(vkey(0, 1, 0), 0, mbx_onesweep_kernel<0, true, false>),
+    MBX_ROW(vkey(0, 1, 1), 0, mbx_onesweep_kernel<0, true, true>),
+    MBX_ROW(vkey(1, 0, 0), 0, mbx_onesweep_kernel<1, false, false>),
+    MBX_ROW(vkey(1, 0, 1), 0, mbx_onesweep_kernel<1, false, true>),
+    MBX_ROW(vkey(1, 1, 0), 0, mbx_onesweep_kernel<1, true, false>),
+    MBX_ROW(vkey(1, 1, 1), 0, mbx_onesweep_kernel<1, true, true>),
+    MBX_ROW(vkey(2, 0, 0), 0, mbx_onesweep_kernel<2, false, false>),
+    MBX_ROW(vkey(2, 0, 1), 0, mbx_onesweep_kernel<2, false, true>),
+    MBX_ROW(vkey(2, 1, 0), 0, mbx_onesweep_kernel<2, true, false>),
+    MBX_ROW(vkey(2, 1, 1), 0, mbx_onesweep_kernel<2, true, true>),
+    MBX_ROW(vkey(3, 0, 0), 0, mbx_onesweep_kernel<3, false, false>),
+    MBX_ROW(vkey(4, 0, 0), ((onesweep_lds_bytes(kMboxSortMaxShards) + 15) & ~(size_t)15) + kPresLdsMax,
+            mbx_onesweep_kernel<4, false, false>),
+};
+// (the persistent form serves stateless views only: at most kStatelessShards shards)
+static const Variant<decltype(mbx_persist_sort_kernel<>)> kPersist[] = {
+    MBX_ROW(vkey(), ((persist_lds_bytes(kStatelessShards) + 15) & ~(size_t)15) + kPresLdsMax, mbx_persist_sort_kernel<>),
+};
+static const Variant<decltype(mbx_drain_msg_kernel<0>)> kDrainMsg[] = {
+    MBX_ROW(vkey(0), 0, mbx_drain_msg_kernel<0>),
+    MBX_ROW(vkey(1), 0, mbx_drain_msg_kernel<kCalculatorMultiply>),
+};
+// (its LDS stage is sized by the 8-shard view: the narrow form)
+static const Variant<decltype(mbx_drain_ring_kernel<0, true, 0>)> kDrainRing[] = {
+    MBX_ROW(vkey(0, 0), 0, mbx_drain_ring_kernel<0, true, 0>),
+    MBX_ROW(vkey(0, 1), 0, mbx_drain_ring_kernel<0, true, 1>),
+    MBX_ROW(vkey(0, 2), 0, mbx_drain_ring_kernel<0, true, 2>),
+    MBX_ROW(vkey(1, 0), 0, mbx_drain_ring_kernel<kCalculatorMultiply, true, 0>),
+    MBX_ROW(vkey(1, 1), 0, mbx_drain_ring_kernel<kCalculatorMultiply, true, 1>),
+    MBX_ROW(vkey(1, 2), 0, mbx_drain_ring_kernel<kCalculatorMultiply, true, 2>),
+};
+
+static std::vector<VariantName> all_variants() {
+  std::vector<VariantName> v;
+  variant_names(kFamCount, kCount, v);
+  variant_names(kFamScatter, kScatter, v);
+  variant_names(kFamOnesweep, kOnesweep, v);
+  variant_names(kFamPersist, kPersist, v);
+  v.push_back({kFamPresence, vkey(), "mbx_presence_kernel<>"});
+  variant_names(kFamDrainMsg, kDrainMsg, v);
+  variant_names(kFamDrainRing, kDrainRing, v);
+  mbx_fused_variants(v);
+  mbx_fused_other_variants(v);
+  mbx_ordered_variants(v);
+  mbx_arrival_variants(v);
+  return v;
+}
+std::vector<std::string> mailbox_variant_names() {
+  std::vector<std::string> out;
+  for (const VariantName& n : all_variants()) out.push_back(n.name);
+  return out;
+}
+std::vector<std::string> mailbox_plan_kernels(const SortPlan& p) {
+  static const std::vector<VariantName> all = all_variants();
+  std::vector<std::string> out;
+  int found[kMbxFamilies] = {};
+  for (const VariantName& n : all)
+    if (p.key[n.family] == n.key) out.push_back(n.name), ++found[n.family];
+  for (int f = 0; f < kMbxFamilies; ++f)
+    if (p.key[f] != kNoKernel && found[f] != 1)
+      throw std::logic_error("mailbox send: the plan's key " + std::to_string(p.key[f]) + " of family " +
+                             std::to_string(f) + " matches " + std::to_string(found[f]) + " variants");
+  return out;
+}
+
+// ---------------------------------------------------------------- host
+// The persistent sort's grid: the blocks the device keeps resident at this LDS size, at most
+// one per tile, a multiple of 8 from 8 up (whole XCD rounds).  (The current device is the Send's.)
+static uint32_t persist_grid(size_t lds, int64_t tiles) {
+  thread_local int c_dev = -1, c_resident = 0;  // the last answer (a Send repeats its device and map size)
+  thread_local size_t c_lds = 0;
+  int dev = 0;
+  PT_HIP_CHECK(hipGetDevice(&dev));
+  if (dev != c_dev || lds != c_lds) {
+    int cus = 0, per_cu = 0;
+    PT_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    PT_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kPersist[0].fn, kST, lds));
+    c_resident = std::max(per_cu, 1) * std::max(cus, 1);
+    c_dev = dev, c_lds = lds;
+  }
+  int64_t g = std::min<int64_t>(c_resident, tiles);
+  if (g >= 8) g -= g % 8;
+  return (uint32_t)g;
+}
+
 uint32_t presence_words(uint32_t n_dir) { return n_dir <= kPresMax ? pres_words(n_dir) : 0u; }
 void launch_presence(uintptr_t dir_rank, uint32_t n_dir, int rank, uintptr_t out, uintptr_t stream) {
   if (n_dir == 0 || n_dir > kPresMax || !dir_rank || !out) throw std::invalid_argument("presence: 1 <= n_dir <= 2^18");
@@ -116,76 +640,117 @@ void launch_presence(uintptr_t dir_rank, uint32_t n_dir, int rank, uintptr_t out
   PT_HIP_CHECK(hipGetLastError());
 }
 
+// A workspace is allocated or grown outside graph capture only.
+static void no_capture(hipStream_t st, const char* what) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    throw std::runtime_error(std::string("mailbox send: ") + what + " inside a graph capture (warm up first)");
+}
+
 // Route mode 4's presence map of this Send's directory: the registry mirror's (rebuilt
 // with the directory) when it is kept for this Send's rank, else folded here, every Send
 // (the directory may have changed since the last one; 128 KB read for 131072 ids).
-void Mailboxes::build_presence(const MboxSend& a, hipStream_t st) {
-  if (a.pres && a.pres_rank == a.rank_self) {
-    pres_view_ = (const uint32_t*)a.pres;
-    return;
-  }
+const uint32_t* Mailboxes::build_presence(const MboxSend& a, hipStream_t st) {
+  if (a.pres && a.pres_rank == a.rank_self) return (const uint32_t*)a.pres;
   const uint32_t nw = pres_words(a.n_dir);
   if (nw > pres_words_) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      throw std::runtime_error("mailbox send: first presence-map Send inside a graph capture (warm up first)");
+    no_capture(st, "first presence-map Send");
     PT_HIP_CHECK(hipStreamSynchronize(st));
     if (pres_) PT_HIP_CHECK(hipFree(pres_));
     PT_HIP_CHECK(hipMalloc((void**)&pres_, (size_t)nw * 4));
     pres_words_ = nw;
   }
-  pres_view_ = pres_;
   hipLaunchKernelGGL(mbx_presence_kernel<>, dim3((nw + 255) / 256), dim3(256), 0, st, (const uint8_t*)a.dir_rank,
                      a.n_dir, a.rank_self, pres_);
   PT_HIP_CHECK(hipGetLastError());
+  return pres_;
 }
 
-void Mailboxes::send_sorted(const MboxSend& a) {
+// The workspaces sized by the batch, grown behind a stream sync; true when it synchronised.
+bool Mailboxes::grow_workspaces(const SortPlan& p, const MboxSend& a, hipStream_t st) {
   const uint32_t S = shards();
-  if (S > (uint32_t)kMboxSortMaxShards) throw std::invalid_argument("sorted mailboxes: at most 1024 shards");
-  if ((uint64_t)S * slots() > 0xfffffffeull) throw std::invalid_argument("sorted mailboxes: shards * slots < 2^32");
-  if (started_ && running()) throw std::runtime_error("mailbox send: a persistent consumer owns the rings");
-  if (a.M <= 0) return;
-  if (!a.actor || !a.a0) throw std::invalid_argument("mailbox send: missing column");
-  if (a.a2 && !mv_.a2) throw std::invalid_argument("mailbox send: 3-argument batch but the rings have no a2 array");
-  if (a.cap == 0 || (a.cap & (a.cap - 1))) throw std::invalid_argument("table capacity must be a power of two");
-  if (!a.out_val || !a.out_st) throw std::invalid_argument("mailbox send: reply outputs required");
-  if ((uint64_t)a.origin_base + (uint64_t)a.M > a.out_n) throw std::invalid_argument("mailbox send: reply view too small");
-  if ((uint64_t)a.origin_base + (uint64_t)a.M > 0x7fffffffull) throw std::invalid_argument("mailbox send: origin >= 2^31");
-  if (a.arrival && a.ordered) throw std::invalid_argument("mailbox send: arrival sharding cannot serve ordered methods");
-  PT_HIP_CHECK(hipSetDevice(device_));
-  hipStream_t st = as_stream(a.stream);
-  const Tune tn = tune();
-  auto capturing = [&] {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  };
-  const int64_t tiles = (a.M + kSTile - 1) / kSTile;
-  if (tiles > 0xffffffffll) throw std::invalid_argument("mailbox send: batch too large");
-  // per-message workspace (route words, ring slots) and per-tile runs: grown outside graph capture
-  if (!a.arrival && (uint64_t)a.M > sort_cap_) {
-    if (capturing()) throw std::runtime_error("mailbox send: a larger batch than before inside a graph capture (warm up first)");
+  bool synced = false;
+  // per-message workspace (route words, ring slots) and per-tile runs
+  if (p.sort_cap > sort_cap_) {
+    no_capture(st, "a larger batch than before");
     PT_HIP_CHECK(hipStreamSynchronize(st));
-    for (void** p : {(void**)&sort_rw_, (void**)&sort_sidx_, (void**)&sort_tinfo_, (void**)&sort_desc_})
-      if (*p) {
-        PT_HIP_CHECK(hipFree(*p));
-        *p = nullptr;
+    for (void** w : {(void**)&sort_rw_, (void**)&sort_sidx_, (void**)&sort_tinfo_, (void**)&sort_desc_})
+      if (*w) {
+        PT_HIP_CHECK(hipFree(*w));
+        *w = nullptr;
       }
-    PT_HIP_CHECK(hipMalloc((void**)&sort_rw_, (size_t)a.M * 4));
-    PT_HIP_CHECK(hipMalloc((void**)&sort_sidx_, (size_t)a.M * 4));
-    PT_HIP_CHECK(hipMalloc((void**)&sort_tinfo_, (size_t)tiles * 2 * S * 4));
+    PT_HIP_CHECK(hipMalloc((void**)&sort_rw_, (size_t)p.sort_cap * 4));
+    PT_HIP_CHECK(hipMalloc((void**)&sort_sidx_, (size_t)p.sort_cap * 4));
+    PT_HIP_CHECK(hipMalloc((void**)&sort_tinfo_, (size_t)p.tiles * 2 * S * 4));
     // look-back descriptors: zero = no tag (every Send's tag is >= 1)
-    PT_HIP_CHECK(hipMalloc((void**)&sort_desc_, (size_t)tiles * S * 8));
-    PT_HIP_CHECK(hipMemsetAsync(sort_desc_, 0, (size_t)tiles * S * 8, st));
+    PT_HIP_CHECK(hipMalloc((void**)&sort_desc_, (size_t)p.tiles * S * 8));
+    PT_HIP_CHECK(hipMemsetAsync(sort_desc_, 0, (size_t)p.tiles * S * 8, st));
     PT_HIP_CHECK(hipStreamSynchronize(st));
-    sort_cap_ = (uint64_t)a.M;
+    sort_cap_ = p.sort_cap;
+    synced = true;
   }
-  if (a.ordered && !stage_rep_) {
-    if (capturing()) throw std::runtime_error("mailbox send: first ordered Send inside a graph capture (warm up first)");
-    const uint64_t n = (uint64_t)S * slots();
+  // 8-B records: the widths word and its pinned mirror, the per-tile field maxima
+  if (p.r8 && (!r8w_ || r8_tiles_ < (uint64_t)p.tiles)) {
+    no_capture(st, "first 8-B-record Send of this size");
+    PT_HIP_CHECK(hipStreamSynchronize(st));
+    if (!r8w_) {
+      // the first Send's widths: the mailbox from the state size or the directory, the rest split
+      const uint32_t nmb = std::max(a.n_state, a.n_dir);
+      uint32_t wm = 20;
+      if (nmb > 1) wm = 32u - (uint32_t)__builtin_clz(nmb - 1);
+      wm = std::max(1u, std::min(wm, 24u));
+      const uint32_t w0 = (52u - wm) / 2, w = wm | (w0 << 8) | ((52u - wm - w0) << 16);
+      PT_HIP_CHECK(hipMalloc((void**)&r8w_, 16));
+      PT_HIP_CHECK(hipMemcpy(r8w_, &w, 4, hipMemcpyHostToDevice));
+      PT_HIP_CHECK(hipHostMalloc((void**)&r8host_, 64, hipHostMallocMapped));
+      *r8host_ = w;
+    }
+    if (r8max_) PT_HIP_CHECK(hipFree(r8max_));
+    PT_HIP_CHECK(hipMalloc((void**)&r8max_, (size_t)p.tiles * 4));
+    r8_tiles_ = (uint64_t)p.tiles;
+    synced = true;
+  }
+  return synced;
+}
+
+// The workspaces a kind of Send allocates once, sized by the rings.
+void Mailboxes::first_use_workspaces(const SortPlan& p, hipStream_t st) {
+  const uint64_t n = (uint64_t)shards() * slots();
+  if (p.need_stage_rep && !stage_rep_) {
+    no_capture(st, "first ordered Send");
     PT_HIP_CHECK(hipMalloc(&stage_rep_, n * 16));
     bytes_ += n * 16;
   }
+  if (p.reserve && !sort_resv_) {
+    no_capture(st, "first reserving Send");
+    PT_HIP_CHECK(hipMalloc((void**)&sort_resv_, (size_t)kMboxSortMaxShards * kResvStride * 4));
+    PT_HIP_CHECK(hipMemset(sort_resv_, 0, (size_t)kMboxSortMaxShards * kResvStride * 4));
+  }
+  if (p.need_r8esc && !r8esc_) {  // escape side array: {a0, mailbox} per ring slot
+    no_capture(st, "first ordered 8-B-record Send");
+    PT_HIP_CHECK(hipMalloc((void**)&r8esc_, n * 16));
+    bytes_ += n * 16;
+  }
+}
+
+SortWs Mailboxes::sort_ws() const {
+  return SortWs{sort_hist_, sort_gsum_, sort_ticket_, sort_rw_, sort_sidx_, sort_tinfo_, sort_desc_,
+                sort_tctr_, r8w_,       r8max_,       r8host_,  r8esc_,     stage_rep_};
+}
+
+void Mailboxes::send_sorted(const MboxSend& a) {
+  const RingGeom g = geometry();
+  if (!validate_sorted(a, g, started_ && running())) return;
+  PT_HIP_CHECK(hipSetDevice(device_));
+  hipStream_t st = as_stream(a.stream);
+  const Tune tn = tune();
+  SortPlan p = plan_sorted(a, tn, g, widths_overflowed());
+  // (behind a stream sync the last Send's verdict on its 8-B widths has landed: read it again)
+  if (grow_workspaces(p, a, st)) p = plan_sorted(a, tn, g, widths_overflowed());
+  first_use_workspaces(p, st);
+  last_plan_ = p;
+  const SortWs ws = sort_ws();
+
   SortIn in{};
   in.actor = (const uint32_t*)a.actor;
   in.a0 = (const int64_t*)a.a0;
@@ -203,338 +768,78 @@ void Mailboxes::send_sorted(const MboxSend& a) {
   in.aw_shift = (a.affine_w && (a.affine_w & (a.affine_w - 1)) == 0) ? __builtin_ctz(a.affine_w) : -1;
   in.rank_self = a.rank_self;
   in.origin_base = a.origin_base;
-  in.tiles = (uint32_t)tiles;
-  // blocks: as many as the histogram holds (it stays L2-resident for the prefixes),
-  // a multiple of 8 (one contiguous eighth of the batch per XCD)
-  int64_t G = std::min<int64_t>({tiles, (int64_t)(kMboxSortHistWords / S), (int64_t)1024,
-                                 (int64_t)kMboxSortGroups * kGroupBlocks});
-  if (G >= 8) G -= G % 8;
-  G = std::max<int64_t>(G, 1);
-  in.G = (uint32_t)G;
-  in.tpb = (uint32_t)((tiles + G - 1) / G);
-  // one block per tile (tile-granular kernels), dealt XCD by XCD: a multiple of 8
-  const uint32_t tile_grid = (uint32_t)(tiles >= 8 ? (tiles + 7) / 8 * 8 : tiles);
-  // the sort: one pass, or count + scatter.  Stateless batches always take the one pass (each
-  // tile reserves its runs: no look-back); ordered ones look back, which a grid under 1024
-  // tiles cannot hide (8 Mi msgs 0.212-0.221 vs 0.228-0.230 ms per Send; 1 Mi msgs 0.047-0.049
-  // vs 0.043 for count + scatter).  Tune mbox_sort=1 / 2 forces either.
-  const int sort_mode = a.sort_mode ? a.sort_mode
-                        : tn.mbox_sort ? tn.mbox_sort
-                        : (tiles >= 1024 || (!a.ordered && !a.arrival)) ? 1 : 2;
-  if (sort_mode < 1 || sort_mode > 2) throw std::invalid_argument("mailbox send: sort_mode 0..2");
-  const bool two_pass = sort_mode == 2;
-  const uint32_t ngroups = two_pass ? (uint32_t)((G + kGroupBlocks - 1) / kGroupBlocks) : 1u;
-  const int mode = (a.affine_w && a.n_dir) ? 2 : (a.dir && a.n_dir) ? 1 : 0;
-  ReplyView rv{(int64_t*)a.out_val, (int32_t*)a.out_st, a.out_n};
-  OutboxView ob;
-  if (a.outbox_cap) {
-    if (a.outbox.size() != 6) throw std::invalid_argument("outbox: [actor, a0, a1, a2, method, count]");
-    ob.actor = (uint32_t*)a.outbox[0];
-    ob.a0 = (int64_t*)a.outbox[1];
-    ob.a1 = (int64_t*)a.outbox[2];
-    ob.a2 = (int64_t*)a.outbox[3];
-    ob.method = (uint16_t*)a.outbox[4];
-    ob.count = (unsigned long long*)a.outbox[5];
-    ob.cap = a.outbox_cap;
-  }
-  const bool fixed_mul = a.fixed_method == kCalculatorMultiply;
-
-  if (a.arrival) {  // fixed positions: enqueue + drain, no count pass
-    last_rec_bytes_ = (a.a2 || a.method_col) ? 32 : 16;
-    last_view_shards_ = S;
-    last_route_ = mode;
-    // both in one launch (mbx_arrival_fused_kernel): an arrival run belongs to one tile, so the
-    // fused form needs no grid-wide phase at any size (tune mbox_fused=0: the two kernels)
-    if (!a.a2 && !a.method_col && tn.mbox_fused != 0) {
-      // rank byte routes for a stateless method on the directory: the records carry actor ids
-      const bool rank_arr = mode == 1 && a.dir_rank && a.n_dir <= kMaxMbox && method_stateless((uint32_t)a.method_uniform);
-      if (rank_arr) last_route_ = 3;
-      // route mode 4 (the directory's presence map in LDS) when it fits -- for batches past 512
-      // tiles: below, the map's staging per block (1024 blocks x 32 KB at 1 Mi) outweighs the
-      // gathers it replaces (config 2: 31.2 vs 29.5 G msg/s)
-      const bool pres_arr = rank_arr && a.n_dir <= kPresMax && tiles > 512;
-      size_t af_lds = 0;
-      if (pres_arr) {
-        build_presence(a, st);
-        in.pres = pres_view_;
-        last_route_ = 4;
-        af_lds = (size_t)pres_words(a.n_dir) * 4;
-        static bool attr = false;
-        if (!attr) {  // (past the 64 KB default for the largest maps)
-          for (const void* k : {(const void*)mbx_arrival_fused_kernel<4, kCalculatorMultiply, 2>,
-                                (const void*)mbx_arrival_fused_kernel<4, kCalculatorMultiply>,
-                                (const void*)mbx_arrival_fused_kernel<4, 0, 2>, (const void*)mbx_arrival_fused_kernel<4, 0>})
-            PT_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)((size_t)pres_words(kPresMax) * 4)));
-          attr = true;
-        }
-      }
-      // 8-B records past 512 tiles (tune mbox_rec8: the sort's rule; per wave, 16 B when a value
-      // of the wave does not fit)
-      const bool allow8 = mv_.planar && (tn.mbox_rec8 == 1 || (tn.mbox_rec8 < 0 && tiles > 512));
-      if (allow8) last_rec_bytes_ = 8;
-      // batches of up to 512 4096-message tiles: 1024-message tiles (four times the blocks)
-      SortIn in1 = in;
-      const bool small_tiles = tiles <= 512;
-      if (small_tiles) in1.tiles = (uint32_t)((a.M + kST * 2 - 1) / (kST * 2));
-      const uint32_t grid1 = in1.tiles >= 8 ? (in1.tiles + 7) / 8 * 8 : in1.tiles;
-#define PT_AFUSED(MO, FX)                                                                                             \
-  do {                                                                                                                \
-    if (small_tiles)                                                                                                  \
-      hipLaunchKernelGGL((mbx_arrival_fused_kernel<MO, FX, 2>), dim3(grid1), dim3(kST), af_lds, st, in1, mv_,         \
-                         (int64_t*)a.state, a.n_state, a.delay_ticks, ob, rv, sort_ticket_, allow8);                  \
-    else                                                                                                              \
-      hipLaunchKernelGGL((mbx_arrival_fused_kernel<MO, FX>), dim3(grid1), dim3(kST), af_lds, st, in1, mv_,            \
-                         (int64_t*)a.state, a.n_state, a.delay_ticks, ob, rv, sort_ticket_, allow8);                  \
-  } while (0)
-      if (fixed_mul) {
-        if (pres_arr) PT_AFUSED(4, kCalculatorMultiply);
-        else if (rank_arr) PT_AFUSED(3, kCalculatorMultiply);
-        else if (mode == 2) PT_AFUSED(2, kCalculatorMultiply);
-        else if (mode == 1) PT_AFUSED(1, kCalculatorMultiply);
-        else PT_AFUSED(0, kCalculatorMultiply);
-      } else {
-        if (pres_arr) PT_AFUSED(4, 0);
-        else if (rank_arr) PT_AFUSED(3, 0);
-        else if (mode == 2) PT_AFUSED(2, 0);
-        else if (mode == 1) PT_AFUSED(1, 0);
-        else PT_AFUSED(0, 0);
-      }
-#undef PT_AFUSED
-      PT_HIP_CHECK(hipGetLastError());
-      return;
-    }
-#define PT_AENQ(MO)                                                                                        \
-  do {                                                                                                     \
-    if (a.a2 && a.method_col)                                                                              \
-      hipLaunchKernelGGL((mbx_arrival_enqueue_kernel<MO, true, true>), dim3(tile_grid), dim3(kST), 0, st, in, mv_, rv);  \
-    else if (a.a2)                                                                                         \
-      hipLaunchKernelGGL((mbx_arrival_enqueue_kernel<MO, true, false>), dim3(tile_grid), dim3(kST), 0, st, in, mv_, rv); \
-    else if (a.method_col)                                                                                 \
-      hipLaunchKernelGGL((mbx_arrival_enqueue_kernel<MO, false, true>), dim3(tile_grid), dim3(kST), 0, st, in, mv_, rv); \
-    else                                                                                                   \
-      hipLaunchKernelGGL((mbx_arrival_enqueue_kernel<MO, false, false>), dim3(tile_grid), dim3(kST), 0, st, in, mv_, rv); \
-  } while (0)
-#define PT_ADRAIN(FX, MO)                                                                                   \
-  hipLaunchKernelGGL((mbx_arrival_drain_kernel<FX, MO>), dim3(tile_grid), dim3(kST), 0, st, mv_, in, (int64_t*)a.state, \
-                     a.n_state, a.delay_ticks, ob, rv, sort_ticket_)
-    if (mode == 2) PT_AENQ(2); else if (mode == 1) PT_AENQ(1); else PT_AENQ(0);
-    PT_HIP_CHECK(hipGetLastError());
-    if (fixed_mul) {
-      if (mode == 2) PT_ADRAIN(kCalculatorMultiply, 2); else if (mode == 1) PT_ADRAIN(kCalculatorMultiply, 1);
-      else PT_ADRAIN(kCalculatorMultiply, 0);
-    } else {
-      if (mode == 2) PT_ADRAIN(0, 2); else if (mode == 1) PT_ADRAIN(0, 1); else PT_ADRAIN(0, 0);
-    }
-#undef PT_AENQ
-#undef PT_ADRAIN
-    PT_HIP_CHECK(hipGetLastError());
-    return;
-  }
-
-  // Stateless batches run on a COARSER view of the same rings: 8 shards of Q * S / 8
-  // slots (every ring is empty between epoch Sends, so any view keeps each actor's
-  // messages in one ring, in message order; ordered batches keep the full S for the
-  // ordered drain's one block per shard).  Longer runs per tile and shard: whole lines
-  // for the sort's stores and the drain's loads (8 Mi msgs, 256 shards -> 32 / 16 / 8:
-  // 0.222 -> 0.186 / 0.179 / 0.180 ms per Send; round 4 with run reservations and 8-B
-  // records: 8 shards 2-3 % faster per bench step than 16, profiles/r4_mailbox_ab.md).
-  MboxView mv = mv_;
-  uint32_t Sv = S;
-  constexpr uint32_t kStatelessShards = 8;
-  if (!a.ordered && kStatelessShards < S) {
-    const uint32_t k = mv.log_s - (uint32_t)__builtin_ctz(kStatelessShards);
-    mv.log_s -= k;
-    mv.log_q += k;
-    Sv = kStatelessShards;
-  }
-  last_view_shards_ = Sv;
-  // the stateless drain: ring order (default) or message order (tune mbox_drain_msg: every slot index written)
-  const bool msg_drain = tn.mbox_drain_msg != 0;
-  const bool all_sidx = msg_drain && !a.ordered;
-  const bool reserve = !a.ordered && sort_mode == 1;  // (one-pass stateless: tiles reserve runs)
-  if (reserve) {
-    if (!sort_resv_) {
-      if (capturing()) throw std::runtime_error("mailbox send: first reserving Send inside a graph capture (warm up first)");
-      PT_HIP_CHECK(hipMalloc((void**)&sort_resv_, (size_t)kMboxSortMaxShards * kResvStride * 4));
-      PT_HIP_CHECK(hipMemset(sort_resv_, 0, (size_t)kMboxSortMaxShards * kResvStride * 4));
-    }
-    mv.resv = sort_resv_;
-  }
-  // Rank byte gathers (route mode 3) for a stateless uniform one-pass Send on the
-  // directory: 1 B per id (L2-resident) instead of the 4-B route word, and the
-  // records carry the actor id -- every actor's messages still meet in one ring
-  // (the shard is a function of the id), and no stateless handler reads a mailbox.
-  const bool rank_route = mode == 1 && a.dir_rank && a.n_dir <= kMaxMbox && !a.ordered && !all_sidx && !a.a2 &&
-                          !a.method_col && method_stateless((uint32_t)a.method_uniform) && sort_mode == 1;
-  last_route_ = rank_route ? 3 : mode;
-  // 8-B ring records: one-pass sort of a batch of one method, at most two arguments for
-  // stateless batches (the ring-order drain) and one for ordered ones (the windowed drain:
-  // 25.5 vs 24.5 G msg/s per 8 Mi SeqFold step, round 5).  Batches up to 512 tiles, which
-  // take the fused kernel, keep 16-B records (1 Mi bench step 24.1 vs 21.9 G msg/s).  Field
-  // widths: the mailbox from the state size or the directory, the rest split between the
-  // zigzag arguments; a stateless record that does not fit spills, an ordered one escapes.
-  const bool r8 = (tn.mbox_rec8 == 1 || (tn.mbox_rec8 < 0 && tiles > 512)) && sort_mode == 1 &&
-                  (!a.ordered || !a.a1) && !a.a2 && !a.method_col && mv.planar && !all_sidx;
-  if (r8 && (!r8w_ || r8_tiles_ < (uint64_t)tiles)) {  // (outside a capture: grown with the sort workspace)
-    if (capturing())
-      throw std::runtime_error("mailbox send: first 8-B-record Send of this size inside a graph capture (warm up first)");
-    PT_HIP_CHECK(hipStreamSynchronize(st));
-    if (!r8w_) {
-      // the first Send's widths: the mailbox from the state size or the directory, the rest split
-      const uint32_t nmb = std::max(a.n_state, a.n_dir);
-      uint32_t wm = 20;
-      if (nmb > 1) wm = 32u - (uint32_t)__builtin_clz(nmb - 1);
-      wm = std::max(1u, std::min(wm, 24u));
-      const uint32_t w0 = (52u - wm) / 2, w = wm | (w0 << 8) | ((52u - wm - w0) << 16);
-      PT_HIP_CHECK(hipMalloc((void**)&r8w_, 16));
-      PT_HIP_CHECK(hipMemcpy(r8w_, &w, 4, hipMemcpyHostToDevice));
-      PT_HIP_CHECK(hipHostMalloc((void**)&r8host_, 64, hipHostMallocMapped));
-      *r8host_ = w;
-    }
-    if (r8max_) PT_HIP_CHECK(hipFree(r8max_));
-    PT_HIP_CHECK(hipMalloc((void**)&r8max_, (size_t)tiles * 4));
-    r8_tiles_ = (uint64_t)tiles;
-  }
-  // fields that outgrew 64 bits (the last Send's widths, bit 31): 16-B records from here on
-  const bool r8_on = r8 && !(__atomic_load_n(r8host_, __ATOMIC_RELAXED) & 0x80000000u);
-  // fields that outgrew 8 B in a stateless batch of a PURE method (its handler reads no actor):
-  // wide pure records, 16 B {a0, a1} + a u16 place, instead of the 32-B long form (the 8 Mi
-  // full-range int64 step writes and reads 18 B per message, not 32)
-  const bool rw_on = r8 && !r8_on && rank_route;  // (rank routes: stateless methods only)
-  last_rec_bytes_ = r8_on ? 8 : rw_on ? 18 : ((a.a2 || a.method_col) ? 32 : 16);  // (16: compact unless a value is wide)
-  if (r8_on && a.ordered && !r8esc_) {  // escape side array: {a0, mailbox} per ring slot
-    if (capturing())
-      throw std::runtime_error("mailbox send: first ordered 8-B-record Send inside a graph capture (warm up first)");
-    const uint64_t n = (uint64_t)S * slots();
-    PT_HIP_CHECK(hipMalloc((void**)&r8esc_, n * 16));
-    bytes_ += n * 16;
-  }
-  if (r8_on) {
+  in.tiles = (uint32_t)p.tiles;
+  in.G = p.G;
+  in.tpb = p.tpb;
+  if (p.r8_on) {
     in.rec8 = 1;
-    in.r8w = r8w_;
-    in.r8max = r8max_;
-    in.r8esc = r8esc_;
-  } else if (rw_on) {
+    in.r8w = ws.r8w;
+    in.r8max = ws.r8max;
+    in.r8esc = ws.r8esc;
+  } else if (p.rw_on) {
     in.recw = 1;
-    in.r8w = r8w_;
-    in.r8max = r8max_;
+    in.r8w = ws.r8w;
+    in.r8max = ws.r8max;
   }
-  const int rf = r8_on ? 1 : rw_on ? 2 : 0;
-  uint32_t* tinfo = all_sidx ? nullptr : sort_tinfo_;
-  if (two_pass) {
-#define PT_COUNT(MO) \
-  hipLaunchKernelGGL((mbx_count_kernel<MO>), dim3(in.G), dim3(kST), 0, st, in, mv.log_s, sort_hist_, sort_gsum_, sort_rw_)
-    if (mode == 2) PT_COUNT(2); else if (mode == 1) PT_COUNT(1); else PT_COUNT(0);
-#undef PT_COUNT
+  if (p.need_pres) in.pres = build_presence(a, st);
+  HandlerArgs h{(int64_t*)a.state, a.n_state, a.delay_ticks, OutboxView{},
+                ReplyView{(int64_t*)a.out_val, (int32_t*)a.out_st, a.out_n}};
+  if (a.outbox_cap) {
+    h.ob.actor = (uint32_t*)a.outbox[0];
+    h.ob.a0 = (int64_t*)a.outbox[1];
+    h.ob.a1 = (int64_t*)a.outbox[2];
+    h.ob.a2 = (int64_t*)a.outbox[3];
+    h.ob.method = (uint16_t*)a.outbox[4];
+    h.ob.count = (unsigned long long*)a.outbox[5];
+    h.ob.cap = a.outbox_cap;
+  }
+  MboxView mv = mv_;  // the plan's view of the rings (stateless batches: coarser)
+  mv.log_s -= p.view_shift;
+  mv.log_q += p.view_shift;
+  if (p.reserve) mv.resv = sort_resv_;
+  if (p.arrival) return mbx_launch_arrival(p, in, mv, ws, h, st);
+  if (p.fused) return mbx_launch_fused(p, in, mv, ws, h, st);
+
+  const uint32_t Sv = p.view_shards;
+  uint32_t* tinfo = p.all_sidx ? nullptr : ws.tinfo;
+  if (p.sort_mode == 2) {
+    auto* count = variant(kCount, p.key[kFamCount]);
+    hipLaunchKernelGGL(count, dim3(in.G), dim3(kST), 0, st, in, mv.log_s, ws.hist, ws.gsum, ws.rw);
     PT_HIP_CHECK(hipGetLastError());
-#define PT_SCAT(A2, MC)                                                                                           \
-  hipLaunchKernelGGL((mbx_scatter_kernel<A2, MC>), dim3(in.G), dim3(kST), scatter_lds_bytes(Sv), st, in, mv,     \
-                     (const uint32_t*)sort_hist_, (const uint32_t*)sort_gsum_, sort_rw_, sort_sidx_, tinfo, rv,      \
-                     !a.ordered, all_sidx)
-    if (a.a2 && a.method_col) PT_SCAT(true, true);
-    else if (a.a2) PT_SCAT(true, false);
-    else if (a.method_col) PT_SCAT(false, true);
-    else PT_SCAT(false, false);
-#undef PT_SCAT
-  } else if (!a.ordered && !all_sidx && fused_ok(tiles)) {
-    // one-pass sort + ring-order drain in ONE launch (mbx_sortdrain_kernel, mailbox_sort_fused.hip)
-    MbxFusedLaunch f{in, mv, sort_desc_, sort_tctr_, sort_gsum_, sort_sidx_, sort_tinfo_, sort_rw_, rv,
-                     (int64_t*)a.state, a.n_state, a.delay_ticks, ob, sort_ticket_, reserve, r8host_,
-                     std::max(onesweep_lds_bytes(Sv), ring_drain_lds_bytes(Sv, kSTile)), st, rf, mode, fixed_mul,
-                     rank_route, a.a2 != 0, a.method_col != 0};
-    mbx_launch_fused(f);
-    return;
+    auto* scatter = variant(kScatter, p.key[kFamScatter]);
+    hipLaunchKernelGGL(scatter, dim3(in.G), dim3(kST), scatter_lds_bytes(Sv), st, in, mv, (const uint32_t*)ws.hist,
+                       (const uint32_t*)ws.gsum, ws.rw, ws.sidx, tinfo, h.rv, !a.ordered, p.all_sidx);
   } else {
-    // route mode 4: a rank-routed Send on a directory whose presence map fits LDS
-    const bool pres_route = rank_route && a.n_dir <= kPresMax;
-    if (pres_route) {
-      build_presence(a, st);
-      in.pres = pres_view_;
-      last_route_ = 4;
+    // route mode 4: the presence map behind the sort's own LDS
+    const size_t map_lds = p.pres_route ? (size_t)pres_words(a.n_dir) * 4 : 0;
+    if (p.pres_route) {
+      variants_allow_lds(kOnesweep);
+      variants_allow_lds(kPersist);
     }
-    const size_t os_lds = pres_route ? ((onesweep_lds_bytes(Sv) + 15) & ~(size_t)15) + (size_t)pres_words(a.n_dir) * 4
-                                     : onesweep_lds_bytes(Sv);
-    // the persistent form of the presence-map sort (mbx_persist_sort_kernel): resident blocks walk the tiles
-    const bool persist = pres_route && persist_ok(tiles);
-    if (pres_route) {
-      static bool attr = false;
-      if (!attr) {  // (past the 64 KB default for the largest maps)
-        PT_HIP_CHECK(hipFuncSetAttribute((const void*)mbx_onesweep_kernel<4, false, false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(((onesweep_lds_bytes(kMboxSortMaxShards) + 15) & ~(size_t)15) +
-                                               (size_t)pres_words(kPresMax) * 4)));
-        // (the persistent form serves stateless views only: at most kStatelessShards shards)
-        PT_HIP_CHECK(hipFuncSetAttribute((const void*)mbx_persist_sort_kernel<>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(((persist_lds_bytes(kStatelessShards) + 15) & ~(size_t)15) +
-                                               (size_t)pres_words(kPresMax) * 4)));
-        attr = true;
-      }
+    if (p.persist) {  // resident blocks walk the tiles
+      const size_t lds = ((persist_lds_bytes(Sv) + 15) & ~(size_t)15) + map_lds;
+      auto* sort = variant(kPersist, p.key[kFamPersist]);
+      hipLaunchKernelGGL(sort, dim3(persist_grid(lds, p.tiles)), dim3(kST), lds, st, in, mv, ws.sidx, tinfo, ws.rw,
+                         h.rv);
+    } else {  // one block per tile, claimed in launch order (the grid is exactly the tile count)
+      const size_t lds = p.pres_route ? ((onesweep_lds_bytes(Sv) + 15) & ~(size_t)15) + map_lds : onesweep_lds_bytes(Sv);
+      auto* sweep = variant(kOnesweep, p.key[kFamOnesweep]);
+      hipLaunchKernelGGL(sweep, dim3(in.tiles), dim3(kST), lds, st, in, mv, ws.desc, ws.tctr, ws.gsum, ws.sidx, tinfo,
+                         ws.rw, h.rv, !a.ordered, p.all_sidx, p.reserve);
     }
-    // one block per tile, claimed in launch order (the grid is exactly the tile count)
-#define PT_OS1(MO, A2, MC)                                                                                        \
-  hipLaunchKernelGGL((mbx_onesweep_kernel<MO, A2, MC>), dim3(in.tiles), dim3(kST), os_lds, st, in,                 \
-                     mv, sort_desc_, sort_tctr_, sort_gsum_, sort_sidx_, tinfo, sort_rw_, rv, !a.ordered, all_sidx,  \
-                     reserve)
-#define PT_OS(MO)                                   \
-  do {                                              \
-    if (a.a2 && a.method_col) PT_OS1(MO, true, true); \
-    else if (a.a2) PT_OS1(MO, true, false);         \
-    else if (a.method_col) PT_OS1(MO, false, true); \
-    else PT_OS1(MO, false, false);                  \
-  } while (0)
-    if (persist) {
-      const size_t ps_lds = ((persist_lds_bytes(Sv) + 15) & ~(size_t)15) + (size_t)pres_words(a.n_dir) * 4;
-      hipLaunchKernelGGL(mbx_persist_sort_kernel<>, dim3(persist_grid(ps_lds, tiles)), dim3(kST), ps_lds, st, in, mv,
-                         sort_sidx_, tinfo, sort_rw_, rv);
-    } else if (pres_route) PT_OS1(4, false, false);
-    else if (rank_route) PT_OS1(3, false, false);
-    else if (mode == 2) PT_OS(2); else if (mode == 1) PT_OS(1); else PT_OS(0);
-#undef PT_OS
-#undef PT_OS1
   }
   PT_HIP_CHECK(hipGetLastError());
   if (a.ordered) {
-    // the ordered drain + the ring-order completion (mailbox_sort_ordered.hip)
-    MbxOrderedLaunch o{};
-    o.in = in, o.mv = mv, o.gsum = sort_gsum_, o.ngroups = ngroups, o.state = (int64_t*)a.state;
-    o.n_state = a.n_state, o.delay_ticks = a.delay_ticks, o.ob = ob, o.stage_rep = (u32x4*)stage_rep_;
-    o.origin_base = a.origin_base, o.Sv = Sv, o.r8_on = r8_on, o.a12 = a.a1 || a.a2;
-    o.fold = a.fixed_method == kSeqFold && !a.method_col;
-    if (r8_on) {
-      o.r8a.r8w = r8w_;
-      o.r8a.method = (uint32_t)a.method_uniform;
-      o.r8a.esc = r8esc_;
-    }
-    o.r8max = r8max_, o.r8w = r8w_, o.r8host = r8host_, o.tinfo = sort_tinfo_, o.rv = rv, o.tctr = sort_tctr_;
-    o.tile_grid = tile_grid, o.st = st;
-    mbx_launch_ordered(o);
-  } else if (msg_drain) {
-#define PT_DMSG(FX)                                                                                              \
-  hipLaunchKernelGGL((mbx_drain_msg_kernel<FX>), dim3(in.G), dim3(kST), 0, st, mv, in, (const uint32_t*)sort_sidx_, \
-                     (const uint32_t*)sort_rw_, (int64_t*)a.state, a.n_state, a.delay_ticks, ob, rv, sort_gsum_,  \
-                     ngroups, sort_ticket_, sort_tctr_)
-    if (fixed_mul) PT_DMSG(kCalculatorMultiply);
-    else PT_DMSG(0);
-#undef PT_DMSG
+    mbx_launch_ordered(p, in, mv, ws, h, st);
+  } else if (p.msg_drain) {
+    auto* drain = variant(kDrainMsg, p.key[kFamDrainMsg]);
+    hipLaunchKernelGGL(drain, dim3(in.G), dim3(kST), 0, st, mv, in, (const uint32_t*)ws.sidx, (const uint32_t*)ws.rw,
+                       h.state, h.n_state, h.delay_ticks, h.ob, h.rv, ws.gsum, p.ngroups, ws.ticket, ws.tctr);
   } else {
-    // the ring-order drain; its LDS stage is sized by the 8-shard view (narrow form)
-#define PT_DRING(FX, RF)                                                                                          \
-  hipLaunchKernelGGL((mbx_drain_ring_kernel<FX, true, RF>), dim3(tile_grid), dim3(kST), ring_drain_lds_bytes(Sv, kSTile), \
-                     st, mv, in, (const uint32_t*)sort_tinfo_, (const uint32_t*)sort_sidx_, (const uint32_t*)sort_rw_, \
-                     (int64_t*)a.state, a.n_state, a.delay_ticks, ob, rv, sort_gsum_, ngroups, sort_ticket_,        \
-                     sort_tctr_, r8host_)
-    if (fixed_mul) {
-      if (rf == 1) PT_DRING(kCalculatorMultiply, 1);
-      else if (rf == 2) PT_DRING(kCalculatorMultiply, 2);
-      else PT_DRING(kCalculatorMultiply, 0);
-    } else {
-      if (rf == 1) PT_DRING(0, 1);
-      else if (rf == 2) PT_DRING(0, 2);
-      else PT_DRING(0, 0);
-    }
-#undef PT_DRING
+    auto* drain = variant(kDrainRing, p.key[kFamDrainRing]);
+    hipLaunchKernelGGL(drain, dim3(p.tile_grid), dim3(kST), ring_drain_lds_bytes(Sv, kSTile), st, mv, in,
+                       (const uint32_t*)ws.tinfo, (const uint32_t*)ws.sidx, (const uint32_t*)ws.rw, h.state, h.n_state,
+                       h.delay_ticks, h.ob, h.rv, ws.gsum, p.ngroups, ws.ticket, ws.tctr, ws.r8host);
   }
   PT_HIP_CHECK(hipGetLastError());
 }

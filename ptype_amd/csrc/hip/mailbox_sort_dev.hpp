@@ -1,11 +1,15 @@
-// Device side of the sorted epoch mailboxes (design notes: mailbox_sort.hip):
-// the kernels and their helpers, all templates, compiled into the launcher TUs
-// that instantiate them -- mailbox_sort.hip (sorts, ring / message-order drains,
-// arrival sharding), mailbox_sort_fused.hip (the fused sort + drain) and
-// mailbox_sort_ordered.hip (the ordered drain and the ring-order completion) --
-// so the variants build in parallel instead of as one long object.
+// What the launcher TUs of the sorted epoch mailboxes share (design notes:
+// mailbox_sort.hip): record forms and decoders, the resolve / rank / reserve
+// helpers and the one-pass sort of a tile, the tile drains the fused kernel
+// shares with the drain kernels, the LDS sizes, and the variant tables' types.
+// A kernel lives in the TU that launches it -- mailbox_sort.hip (sorts, ring /
+// message-order drains), mailbox_sort_fused.hip (the fused sort + drain),
+// mailbox_sort_ordered.hip (the ordered drain and the ring-order completion),
+// mailbox_sort_arrival.hip (arrival sharding) -- so the variants build in
+// parallel instead of as one long object.
 #pragma once
 #include <algorithm>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -20,15 +24,8 @@ namespace ptype {
 namespace {
 constexpr uint32_t kCompactMark = 0x80000000u;
 constexpr uint32_t kCompactLong = 0x80000000u;
-constexpr int kOrdThreads = 512;  // ordered drain: one block per shard, one bin per thread
-constexpr int kOrdK = 4;
-constexpr int kOrdWin = kOrdThreads * kOrdK;  // records per window (2048)
-constexpr int kOrdWaves = kOrdThreads / kWave;
-constexpr uint32_t kOrdStateMax = 4096;  // a shard's actors whose state is staged in LDS (32 KB)
 }  // namespace
 
-// ---------------------------------------------------------------- K2s pass 1: count
-constexpr uint32_t kGroupBlocks = 32;  // the scatter's prefix: group sums + rows inside the group
 constexpr uint32_t kNoSlot = 0xffffffffu;
 // A stateless batch's message whose shard ring is full SPILLS: the parallel drain
 // runs it straight from the batch (its route word + argument columns) in message
@@ -41,202 +38,6 @@ constexpr uint32_t kRunSpilled = 0x80000000u;  // tinfo count word: the run did 
 // The builtin, not inline assembly: the compiler's wait insertion reads it and then knows that no
 // load is outstanding, so it adds no waits of its own behind it.
 constexpr int kWaitVmcnt0 = 0x0f70;
-
-template <int MODE>
-__global__ __launch_bounds__(kST) void mbx_count_kernel(SortIn in, uint32_t log_s, uint32_t* __restrict__ hist,
-                                                        uint32_t* __restrict__ gsum, uint32_t* __restrict__ rw) {
-  __shared__ uint32_t cnt[kMboxSortMaxShards];
-  const uint32_t S = 1u << log_s;
-  const uint32_t v = virt_block(blockIdx.x, in.G);
-  for (uint32_t s = threadIdx.x; s < S; s += kST) cnt[s] = 0;
-  __syncthreads();
-  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
-  uint32_t a[kSK];
-  if (t0 < t1) load_actors(in, t0, a);
-  for (uint32_t t = t0; t < t1; ++t) {
-    int r[kSK];
-    uint32_t mb[kSK];
-    resolve_k<MODE>(in, a, r, mb);
-    if (t + 1 < t1) load_actors(in, t + 1, a);  // next tile's loads in flight while this one counts
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      const int64_t i = tile_index(t, k);
-      const bool ok = r[k] == in.rank_self && mb[k] < kMaxMbox;
-      if (i < in.M) rw[i] = ok ? mb[k] : kNoSlot;
-      if (ok) atomicAdd(&cnt[mb[k] & (S - 1)], 1u);
-    }
-  }
-  __syncthreads();
-  uint32_t* g = gsum + (size_t)(v / kGroupBlocks) * S;
-  for (uint32_t s = threadIdx.x; s < S; s += kST) {
-    const uint32_t c = cnt[s];
-    hist[(size_t)v * S + s] = c;
-    if (c) atomicAdd(&g[s], c);
-  }
-}
-
-// ---------------------------------------------------------------- K2s pass 2: scatter
-// The tile's arguments are loaded with its route words, before the ranking (in
-// flight across it).  Loading them only once the ranks are known (a smaller
-// register file, occupancy 4 -> 5) measured slower: 124 -> 164 us per 8 Mi.
-template <bool A2, bool MC>
-__device__ __forceinline__ void load_routed(const SortIn& in, const uint32_t* __restrict__ rw, uint32_t t,
-                                            uint32_t (&m)[kSK], int64_t (&x0)[kSK], int64_t (&x1)[kSK],
-                                            int64_t (&x2)[kSK], uint32_t (&meth)[kSK]) {
-#pragma unroll
-  for (int k = 0; k < kSK; ++k) {
-    const int64_t i = tile_index(t, k);
-    const bool ok = i < in.M;
-    m[k] = ok ? __builtin_nontemporal_load(rw + i) : kNoSlot;
-    x0[k] = ok ? __builtin_nontemporal_load(in.a0 + i) : 0;
-    x1[k] = ok && in.a1 ? __builtin_nontemporal_load(in.a1 + i) : 0;
-    x2[k] = 0;
-    if constexpr (A2) x2[k] = ok ? __builtin_nontemporal_load(in.a2 + i) : 0;
-    meth[k] = in.method_uniform;
-    if constexpr (MC) meth[k] = ok ? (uint32_t)in.mcol[i] : 0u;
-  }
-}
-
-// Per-tile runs (`tinfo`, [tiles][2][S] u32): tile t's records of shard s sit at
-// ring slots s | ((bias + j) & (Q - 1)), j < count (bias = epoch-start tail +
-// the run's offset + the shard's rotation; count clamped to the free room, its
-// top bit set when the run spilled / overflowed the room) -- what the ring-order
-// drain and completion read instead of a per-message slot index.  The slot
-// index `sidx` is written only where a consumer needs it: every message with
-// `all_sidx` (the message-order drain, tune mbox_drain_msg=1), and the whole
-// tile when some message of it spilled (the drain runs that tile in message
-// order).  (An opt-in LDS-staged write-out in ring order measured slower,
-// 117 -> 161 us per 8 Mi msgs: the 80 KB stage halved the resident blocks;
-// removed, see git history 4c4ea76.)
-__host__ __device__ constexpr size_t scatter_lds_bytes(uint32_t S) { return (size_t)S * (16 + 4 * (kST / kWave)); }
-
-template <bool A2, bool MC>
-__global__ __launch_bounds__(kST) void mbx_scatter_kernel(SortIn in, MboxView mv, const uint32_t* __restrict__ hist,
-                                                          const uint32_t* __restrict__ gsum,
-                                                          uint32_t* __restrict__ rw,
-                                                          uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
-                                                          ReplyView rv, bool spill, bool all_sidx) {
-  // LDS sized by the shard count (16 + 4 * waves B per shard): occupancy is not
-  // capped by the 1024-shard maximum
-  extern __shared__ __align__(16) unsigned char smem_sc[];
-  const uint32_t S = 1u << mv.log_s;
-  unsigned long long* base = reinterpret_cast<unsigned long long*>(smem_sc);  // ring position of offset 0 (tail)
-  uint32_t* run = reinterpret_cast<uint32_t*>(base + S);  // this block's next offset per shard
-  uint32_t* room = run + S;                               // offset limit (free ring slots)
-  uint32_t* wcnt_all = room + S;                          // [kST / kWave][S] per-wave counts -> wave offsets
-  auto wcnt = [&](unsigned ww, uint32_t sh) -> uint32_t& { return wcnt_all[ww * S + sh]; };
-  const uint64_t Q = 1ull << mv.log_q;
-  const uint32_t v = virt_block(blockIdx.x, in.G);
-  const unsigned w = threadIdx.x / kWave, lane = lane_id();
-  const uint32_t g0 = v / kGroupBlocks, v0 = g0 * kGroupBlocks;
-  for (uint32_t s = threadIdx.x; s < S; s += kST) {
-    // this block's prefix: whole groups before it, then the rows before it in its group
-    uint32_t p = 0;
-    for (uint32_t g = 0; g < g0; ++g) p += gsum[(size_t)g * S + s];
-    for (uint32_t u = v0; u < v; ++u) p += hist[(size_t)u * S + s];
-    run[s] = p;
-    const uint64_t tl = *ctr_tail(mv, s), hd = *ctr_head(mv, s);
-    base[s] = tl;
-    const uint64_t free = hd + Q > tl ? hd + Q - tl : 0;
-    room[s] = (uint32_t)(free < 0xffffffffull ? free : 0xffffffffull);
-  }
-  unsigned long long n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;
-  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
-  for (uint32_t t = t0; t < t1; ++t) {
-    for (uint32_t s = lane; s < S; s += kWave) wcnt(w, s) = 0;  // this wave's row only
-    uint32_t mb[kSK], meth[kSK];
-    int64_t v0[kSK], v1[kSK], v2[kSK];
-    load_routed<A2, MC>(in, rw, t, mb, v0, v1, v2, meth);
-    // rank of each message among this wave's earlier messages of its shard
-    uint32_t wr[kSK], sh[kSK];
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      const bool ok = mb[k] != kNoSlot;
-      sh[k] = mb[k] & (S - 1);
-      const uint64_t peers = match_bits(sh[k], mv.log_s, __ballot(ok));
-      const unsigned below = mbcnt64(peers);
-      const int leader = peers ? __builtin_ctzll(peers) : 0;
-      unsigned old = 0;
-      if (ok && below == 0) {  // group leader: one plain LDS read-add per distinct shard of the wave
-        old = wcnt(w, sh[k]);
-        wcnt(w, sh[k]) = old + (unsigned)__popcll(peers);
-      }
-      wr[k] = (unsigned)__shfl((int)old, leader) + below;
-    }
-    __syncthreads();
-    int sp = 0;
-    for (uint32_t s = threadIdx.x; s < S; s += kST) {  // wave offsets in message order, then the block's run
-      uint32_t rr = run[s];
-#pragma unroll
-      for (int ww = 0; ww < kST / kWave; ++ww) {
-        const uint32_t c = wcnt(ww, s);
-        wcnt(ww, s) = rr;
-        rr += c;
-      }
-      run[s] = rr;
-      sp |= rr > room[s];
-    }
-    bool tile_spill = false;  // (either barrier publishes the wave offsets too)
-    if (spill) tile_spill = __syncthreads_or(sp) != 0;
-    else __syncthreads();
-    const bool wsidx = all_sidx || tile_spill;
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      const int64_t i = tile_index(t, k);
-      if (i >= in.M) continue;
-      const uint32_t origin = in.origin_base + (uint32_t)i;
-      if (mb[k] == kNoSlot) {
-        ++n_miss;
-        if (wsidx) sidx[i] = kNoSlot;
-        write_status(rv, origin, kStatusNoActor);
-        continue;
-      }
-      const uint32_t off = wcnt(w, sh[k]) + wr[k];
-      if (off >= room[sh[k]]) {  // the ring is full
-        if (spill) {  // stateless batch: the drain runs it from the batch
-          ++n_spill;
-          sidx[i] = kSpillSlot;
-          continue;
-        }
-        ++n_ovf;  // answered now, re-sent by send_all
-        if (wsidx) sidx[i] = kNoSlot;
-        write_status(rv, origin, kStatusOverflow);
-        continue;
-      }
-      const int64_t x0 = v0[k], x1 = v1[k], x2 = v2[k];
-      const uint32_t mt = meth[k];
-      const uint64_t slot = slot_at(mv, sh[k], base[sh[k]] + off);
-      if (wsidx) sidx[i] = (uint32_t)slot;
-      if (mt < 128u && fits_i32(x0) && fits_i32(x1) && x2 == 0) {
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | (mt << 24), (uint32_t)x0, (uint32_t)x1};
-      } else {
-        const uint32_t fl = x2 != 0 ? (uint32_t)kFlagA2 : 0u;
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | kCompactLong, (mt & 0xffffu) | (fl << 16), 0u};
-        *reinterpret_cast<u32x4*>(rec_b(mv, slot)) =
-            u32x4{(uint32_t)x0, (uint32_t)((uint64_t)x0 >> 32), (uint32_t)x1, (uint32_t)((uint64_t)x1 >> 32)};
-        if (fl) mv.a2[slot] = x2;
-      }
-      ++n_enq;
-    }
-    if (tinfo) {  // the tile's runs (after the stores: the messages' registers are dead by now -- +25 VGPRs above)
-      // slot bias from the epoch-start tail (a drain may commit before the completion reads it)
-      for (uint32_t s = threadIdx.x; s < S; s += kST) {
-        const uint32_t r0 = wcnt(0, s), rr = run[s];  // wave 0's offset = the run before this tile
-        const uint32_t cc = r0 >= room[s] ? 0u : min(rr - r0, room[s] - r0);
-        tinfo[(size_t)t * 2 * S + s] = (uint32_t)(base[s] + r0) + shard_rot(mv, s);
-        tinfo[(size_t)t * 2 * S + S + s] = cc | (rr > room[s] ? kRunSpilled : 0u);
-      }
-    }
-    __syncthreads();  // wcnt rows are reused by the next tile
-  }
-  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_ovf, kMbOverflow, n_miss, kMbNoActor);
-  if (spill) {
-    __syncthreads();  // block_add_stats' LDS partials are reused
-    block_add_stats(mv.stats, n_spill, kMbSpilled, 0, -1, 0, -1);
-  }
-}
 
 // ---------------------------------------------------------------- K2s one pass: resolve + look-back + scatter
 // The count and scatter passes as ONE kernel (a single-pass counting sort with
@@ -353,28 +154,6 @@ __device__ __forceinline__ void rec8_next_from(const uint32_t* r8max, uint32_t* 
 // in LDS (32 KB for 131072 ids) and resolves each message with an LDS read instead of a
 // scattered global gather: 64 lanes gathering from 64 lines kept the sort's address unit
 // stalled by the texture cache half its busy time (profiles/r6_pmc_head.txt).
-constexpr uint32_t kPresMax = 1u << 18;  // ids (64 KB of map)
-__host__ __device__ constexpr uint32_t pres_words(uint32_t n_dir) { return ((n_dir + 15) / 16 + 3) & ~3u; }
-template <int = 0>
-__global__ __launch_bounds__(256) void mbx_presence_kernel(const uint8_t* __restrict__ dirr, uint32_t n_dir,
-                                                           int rank_self, uint32_t* __restrict__ pres) {
-  const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
-  if (wi >= pres_words(n_dir)) return;
-  alignas(16) uint8_t b[16];
-  if (wi * 16 + 16 <= n_dir) {  // (the table is a whole allocation: 16-B aligned)
-    *reinterpret_cast<uint4*>(b) = *reinterpret_cast<const uint4*>(dirr + (size_t)wi * 16);
-  } else {
-#pragma unroll
-    for (uint32_t j = 0; j < 16; ++j) b[j] = wi * 16 + j < n_dir ? dirr[wi * 16 + j] : kRankMissing;
-  }
-  uint32_t w = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) {
-    const uint32_t st = b[j] == (uint8_t)rank_self ? 1u : b[j] == kRankFallback ? 2u : 0u;
-    w |= st << (2 * j);
-  }
-  pres[wi] = w;
-}
 __device__ __forceinline__ void stage_pres(const SortIn& in, uint32_t* lpres) {
   const uint32_t nw = pres_words(in.n_dir);
   for (uint32_t w = threadIdx.x * 4; w < nw; w += blockDim.x * 4)
@@ -683,188 +462,6 @@ __device__ __forceinline__ uint32_t onesweep_tile(const SortIn& in, const MboxVi
   return t;
 }
 
-template <int MODE, bool A2, bool MC>
-__global__ __launch_bounds__(kST) void mbx_onesweep_kernel(SortIn in, MboxView mv, unsigned long long* __restrict__ desc,
-                                                           unsigned* __restrict__ tctr, uint32_t* __restrict__ gsum,
-                                                           uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
-                                                           uint32_t* __restrict__ rw, ReplyView rv, bool spill,
-                                                           bool all_sidx, bool reserve) {
-  extern __shared__ __align__(16) unsigned char smem_os[];
-  (void)onesweep_tile<MODE, A2, MC>(in, mv, desc, tctr, gsum, sidx, tinfo, rw, rv, spill, all_sidx, smem_os, reserve);
-}
-
-// ---------------------------------------------------------------- K2s persistent reserving sort
-// The reserving one-pass sort of a presence-map Send (route mode 4) as a grid of
-// resident blocks, each walking several tiles (tune mbox_persist).  What a tile of
-// mbx_onesweep_kernel<4> repeats and a Send needs once is done once per block: the map
-// staged in LDS, each ring's tail and room read, the enqueue counters added.  And the
-// tile's serial chain of round trips is shortened by running one tile ahead on the cheap
-// column: tile i+1's actor loads are issued before tile i's record stores, it is resolved
-// and ranked right after them, and its runs' reservations (one returning atomic per shard)
-// come back behind tile i+1's argument loads.  Only the next tile's actors / mailboxes and
-// packed ranks (12 registers) cross an iteration whole; the arguments are never held a tile
-// ahead of their stores (the 208-VGPR form, profiles/r5_mailbox_ab.md).  The prefixes, the
-// wave offsets and the spill vote's flag word are double-buffered in LDS, so a tile costs
-// two barriers: one between its votes / prefixes and its stores, one between the next
-// tile's ranking and its reservations.
-//
-// What is in flight where (profiles/sort_drain_waits.md).  Tile i+1's 16 argument loads are
-// issued directly behind tile i's last record store -- the registers are dead there -- and
-// cross tile i+1's resolve, ranking, barrier and reservation, none of which waits for
-// memory (the actors came in with tile i's arguments).  A whole tile's argument loads carry
-// no bounds branches (load_args_tile).  At the top of iteration i+1 tile i+2's actor loads
-// go out behind them; then ONE wait takes in all of them (os_loads_in), on every path, ahead
-// of the barrier: from there to the tile's last record store no instruction waits on vmcnt,
-// so the stores -- which count in vmcnt on gfx950 -- issue back to back.  The vote is a flag
-// word a wave sets before the first barrier when a lane spills, read behind it, cleared
-// behind the second (in place of __syncthreads_or: three barriers around an LDS word).
-//
-// Tiles: no counter, no flag, no block waits for another.  Block b of G (a multiple of 8
-// where there are 8 or more) sits on XCD b % 8; with a tile count that is a multiple of 8
-// it takes tiles x * T/8 + j, j = b / 8 + i * G/8 -- the XCD virt_block gives each tile in
-// the one-tile-per-block form, which is where the ring drain reads its runs.  Otherwise
-// tile b + i * G.  A tile's runs land in the rings in the order the blocks reserve them,
-// which a stateless ring allows (see onesweep_tile).
-__host__ __device__ constexpr size_t persist_lds_bytes(uint32_t S) {
-  return (size_t)S * (8 + 4 + 2 * 4 + 2 * 4 * (kST / kWave));
-}
-
-template <int = 0>
-__global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx,
-                                                               uint32_t* __restrict__ tinfo, uint32_t* __restrict__ rw,
-                                                               ReplyView rv) {
-  constexpr int SK = kSK;
-  extern __shared__ __align__(16) unsigned char smem_ps[];
-  const uint32_t S = 1u << mv.log_s;
-  unsigned long long* base = reinterpret_cast<unsigned long long*>(smem_ps);  // each ring's epoch-start tail
-  uint32_t* room = reinterpret_cast<uint32_t*>(base + S);                     // offset limit past the tail
-  uint32_t* pre2 = room + S;                                                  // [2][S] a tile's prefix per shard
-  uint32_t* wcnt2 = pre2 + 2 * S;                                             // [2][kST / kWave][S]
-  uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_ps + ((persist_lds_bytes(S) + 15) & ~(size_t)15));
-  __shared__ uint32_t tmax[3];
-  __shared__ uint32_t vote[2];  // the spill vote's flag word of a tile, double-buffered like pre / wcnt
-  const unsigned w = threadIdx.x / kWave, lane = lane_id();
-  // this block's tiles: first, first + stride, ... (n of them)
-  const uint32_t G = gridDim.x, T = in.tiles;
-  uint32_t first = blockIdx.x, stride = G, n = blockIdx.x < T ? (T - blockIdx.x + G - 1) / G : 0u;
-  if (G >= 8 && (G & 7) == 0 && (T & 7) == 0) {
-    const uint32_t j = blockIdx.x >> 3, T8 = T >> 3;
-    stride = G >> 3;
-    first = (blockIdx.x & 7) * T8 + j;
-    n = j < T8 ? (T8 - j + stride - 1) / stride : 0u;
-  }
-  if (n == 0) return;
-  // once per block: the map, the rings' tails and room
-  stage_pres(in, lpres);
-  for (uint32_t s = threadIdx.x; s < S; s += kST) {
-    uint64_t tl;
-    room[s] = os_ring_room(mv, s, tl);
-    base[s] = tl;
-  }
-  if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
-  if (threadIdx.x < 2) vote[threadIdx.x] = 0;
-  for (uint32_t s = lane; s < S; s += kWave) wcnt2[w * S + s] = 0;
-  __syncthreads();
-  const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
-  const bool maxima = in.rec8 || in.recw;
-  uint32_t n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;  // (a block's share of a batch: below 2^32)
-  // the first tile, up to its reservations in flight; its arguments behind its actors
-  uint32_t nx[SK];  // the coming tile: actors, then mailboxes
-  int64_t v0[SK], v1[SK];  // the coming tile's arguments, in flight from behind the last tile's stores
-  PackedRanks<SK> wrp;
-  {
-    uint32_t a[SK], wr[SK];
-    int r[SK];
-    const bool full = tile_is_full<SK>(in, first);
-    load_actors<SK>(in, first, a);
-    load_args_tile<SK>(in, first, full, v0, v1);
-    os_resolve<4, SK>(in, lpres, a, r, nx);
-    os_rank<SK>(in, mv.log_s, first, r, nx, wcnt2 + w * S, wr);
-#pragma unroll
-    for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
-  }
-  __syncthreads();
-  // (S <= kST: a shard's thread keeps its run's count and reserved offset in registers)
-  uint32_t rc = 0, rx = 0;
-  if (threadIdx.x < S) {
-    rc = os_wave_offsets(wcnt2, S, threadIdx.x);
-    rx = os_reserve(mv, threadIdx.x, rc);
-  }
-  for (uint32_t it = 0; it < n; ++it) {
-    const uint32_t t = first + it * stride, b = it & 1;
-    uint32_t* pre = pre2 + b * S;
-    uint32_t* wcnt_all = wcnt2 + b * (kST / kWave) * S;
-    const bool full = tile_is_full<SK>(in, t);
-    uint32_t mb[SK];
-#pragma unroll
-    for (int k = 0; k < SK; ++k) mb[k] = nx[k];
-    // the next tile's actors (in flight across this tile's stores), behind this tile's arguments and its
-    // reservations, both issued a tile ago
-    const bool more = it + 1 < n;
-    const bool full_next = more && tile_is_full<SK>(in, t + stride);
-    if (more) load_actors<SK>(in, t + stride, nx);
-    // the one wait for the tile's loads, on every path: nothing below, up to the last record store, waits
-    // for memory again -- not for the run words' stores either (the next tile's actors are in with the
-    // arguments: its ranking follows the stores)
-    os_loads_in<SK>(v0, v1, nx);
-    int sp = 0;
-    if (threadIdx.x < S) {
-      const uint32_t s = threadIdx.x;
-      pre[s] = rx;
-      sp = os_run_info(mv, tinfo, t, S, s, base[s], room[s], rx, rc);
-    }
-    const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
-    sp |= escm != 0;
-    // the spill vote: a wave with a spilling lane sets this tile's flag word, read behind the tile's barrier
-    if (__any(sp) && lane == 0) vote[b] = 1u;
-    __syncthreads();
-    const bool tile_spill = __builtin_amdgcn_readfirstlane((int)vote[b]) != 0;  // (block-uniform: a scalar)
-    if (threadIdx.x == 0) {
-      // (a tile spilled by its records' widths: flagged for the drains, as in onesweep_tile)
-      if (tile_spill) tinfo[(size_t)t * 2 * S + S] |= kRunSpilled;
-      if (maxima) {  // the tile's field bit lengths; cleared for the next tile (its maxima follow a barrier)
-        (void)atomicExch(&in.r8max[t], tmax[0] | (tmax[1] << 8) | (tmax[2] << 16));
-        tmax[0] = tmax[1] = tmax[2] = 0;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      const int64_t i = tile_index<SK>(t, k);
-      if (!full && i >= in.M) continue;
-      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], 0, in.method_uniform,
-                       (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
-    }
-    if (more) {
-      // the next tile's arguments, right behind this tile's stores: in flight across its resolve, rank,
-      // barrier and reservation
-      load_args_tile<SK>(in, t + stride, full_next, v0, v1);
-      // the next tile in the other buffer (last read before this tile's barrier): resolved, ranked, reserved
-      uint32_t* wnext = wcnt2 + (b ^ 1) * (kST / kWave) * S;
-      for (uint32_t s = lane; s < S; s += kWave) wnext[w * S + s] = 0;
-      uint32_t a[SK], wr[SK];
-      int r[SK];
-#pragma unroll
-      for (int k = 0; k < SK; ++k) a[k] = nx[k];
-      os_resolve<4, SK>(in, lpres, a, r, nx);
-      os_rank<SK>(in, mv.log_s, t + stride, r, nx, wnext + w * S, wr);
-#pragma unroll
-      for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
-      __syncthreads();
-      // (every thread has read this tile's flag word: cleared for the tile after the next, whose votes
-      // follow the next tile's barrier)
-      if (threadIdx.x == 0) vote[b] = 0u;
-      if (threadIdx.x < S) {
-        rc = os_wave_offsets(wnext, S, threadIdx.x);
-        rx = os_reserve(mv, threadIdx.x, rc);
-      }
-    }
-  }
-  // once per block: the enqueue counters
-  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_ovf, kMbOverflow, n_miss, kMbNoActor);
-  __syncthreads();  // block_add_stats' LDS partials are reused
-  block_add_stats(mv.stats, n_spill, kMbSpilled, 0, -1, 0, -1);
-}
-
 // ---------------------------------------------------------------- compact record decode
 struct SortRec {
   uint32_t origin, mb, method, flags;
@@ -1051,31 +648,6 @@ __device__ __forceinline__ void drain_tile_msg(MboxView mv, SortIn in, uint32_t 
     failed += rr.status != kStatusOk;
     write_reply(rv, origin, rr);
     ++done;
-  }
-}
-
-template <int FIXED>
-__global__ __launch_bounds__(kST) void mbx_drain_msg_kernel(MboxView mv, SortIn in, const uint32_t* __restrict__ sidx,
-                                                            const uint32_t* __restrict__ rw,
-                                                            int64_t* __restrict__ state, uint32_t n_state,
-                                                            uint64_t delay_ticks, OutboxView ob, ReplyView rv,
-                                                            uint32_t* __restrict__ gsum, uint32_t ngroups,
-                                                            unsigned* __restrict__ ticket, unsigned* __restrict__ tctr) {
-  // the scatter's block -> tile ranges: a tile's records sit in ~S short runs that
-  // this block's waves read whole (line reuse in L1 / L2), not one record per block
-  unsigned long long done = 0, failed = 0, holes = 0;
-  const uint32_t v = virt_block(blockIdx.x, in.G);
-  const uint32_t t0 = v * in.tpb, t1 = min(t0 + in.tpb, in.tiles);
-  for (uint32_t t = t0; t < t1; ++t)
-    drain_tile_msg<FIXED>(mv, in, t, sidx, rw, state, n_state, delay_ticks, ob, rv, done, failed, holes);
-  block_add_stats(mv.stats, done, kMbProcessed, failed, kMbFailed, holes, kMbHoles);
-  __shared__ bool last;
-  if (threadIdx.x == 0) last = last_block_ticket(ticket);
-  __syncthreads();
-  if (last) {  // every block's records are read: the rings are consumed
-    const uint32_t S = 1u << mv.log_s;
-    for (uint32_t s = threadIdx.x; s < S; s += kST) epoch_commit(mv, s, epoch_sum(mv, gsum, ngroups, S, s));
-    if (threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag
   }
 }
 
@@ -1268,784 +840,74 @@ __device__ __forceinline__ DrainCounts drain_ring_tile(MboxView mv, SortIn in, u
   return DrainCounts{done, failed, holes};
 }
 
-template <int FIXED, bool NARROW, int RF, int SK = kSK>
-__global__ __launch_bounds__(kST, (NARROW && FIXED) ? 8 : 1) void mbx_drain_ring_kernel(MboxView mv, SortIn in, const uint32_t* __restrict__ tinfo,
-                                                             const uint32_t* __restrict__ sidx,
-                                                             const uint32_t* __restrict__ rw,
-                                                             int64_t* __restrict__ state, uint32_t n_state,
-                                                             uint64_t delay_ticks, OutboxView ob, ReplyView rv,
-                                                             uint32_t* __restrict__ gsum, uint32_t ngroups,
-                                                             unsigned* __restrict__ ticket, unsigned* __restrict__ tctr,
-                                                             uint32_t* __restrict__ r8host) {
-  extern __shared__ __align__(16) unsigned char smem_rd[];
-  const uint32_t S = 1u << mv.log_s;
-  DrainCounts dc;
-  // tiles dealt XCD by XCD like the scatter's blocks (whose writes the XCD's L2 may still hold)
-  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
-  if (t < in.tiles)
-    dc = drain_ring_tile<FIXED, NARROW, false, RF, SK>(mv, in, t, tinfo, sidx, rw, state, n_state, delay_ticks, ob,
-                                                       rv, smem_rd);
-  block_add_stats(mv.stats, dc.done, kMbProcessed, dc.failed, kMbFailed, dc.holes, kMbHoles);
-  __shared__ bool last;
-  if (threadIdx.x == 0) last = last_block_ticket(ticket);
-  __syncthreads();
-  if (last) {  // every block's records are read: the rings are consumed
-    for (uint32_t s = threadIdx.x; s < S; s += kST) epoch_commit(mv, s, epoch_sum(mv, gsum, ngroups, S, s));
-    if (threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag
-    if constexpr (RF != 0) rec8_next(in, const_cast<uint32_t*>(in.r8w), r8host, in.tiles);
-  }
-}
+// ---------------------------------------------------------------- kernel variant tables
+// A family's instantiations, listed: a row is the key of a variant (vkey of the template
+// arguments the family varies, as the plan computes it), the dynamic LDS it may ask for
+// past the 64 KB default (0: never more), its name and the kernel.  The tables ARE the set
+// of kernels a Send can launch: a variant is added or removed as one row.
+template <class Fn>
+struct Variant {
+  uint32_t key;
+  size_t max_lds;
+  const char* name;
+  Fn* fn;
+};
+#define MBX_ROW(key, max_lds, ...) {key, max_lds, #__VA_ARGS__, __VA_ARGS__}
 
-// ---------------------------------------------------------------- fused one-pass sort + ring-order drain
-// Batches of stateless methods (the parallel drain): the block that sorts tile t
-// into the rings drains tile t's runs right after -- the runs of a tile are
-// exactly the records it wrote, so no other block's progress is needed, only a
-// barrier between the block's stores and its ring-order reads (FRESH loads).
-// The records still go through the rings (written, then read back in ring
-// order by other lanes than wrote them), but the Send is one launch instead of
-// two, the drain's reads are L2 hits of lines the sort just wrote, and no block
-// waits at a kernel boundary for the slowest tile.  The last block to finish
-// commits every shard's epoch (tail = head = tail + total) and advances the
-// look-back tag.  Tune mbox_fused=0: the separate kernels.
-template <int MODE, bool A2, bool MC, int FIXED, int RF, int SK = kSK>
-__global__ __launch_bounds__(kST) void mbx_sortdrain_kernel(SortIn in, MboxView mv, unsigned long long* __restrict__ desc,
-                                                            unsigned* __restrict__ tctr, uint32_t* __restrict__ gsum,
-                                                            uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
-                                                            uint32_t* __restrict__ rw, ReplyView rv,
-                                                            int64_t* __restrict__ state, uint32_t n_state,
-                                                            uint64_t delay_ticks, OutboxView ob,
-                                                            unsigned* __restrict__ ticket, bool reserve,
-                                                            uint32_t* __restrict__ r8host) {
-  extern __shared__ __align__(16) unsigned char smem_sd[];
-  const uint32_t S = 1u << mv.log_s;
-  const uint32_t t = onesweep_tile<MODE, A2, MC, SK>(in, mv, desc, tctr, gsum, sidx, tinfo, rw, rv, true, false,
-                                                     smem_sd, reserve);
-  // every wave's ring stores are out before any wave reads the tile's runs
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const DrainCounts dc = drain_ring_tile<FIXED, true, true, RF, SK>(mv, in, t, tinfo, sidx, rw, state, n_state,
-                                                                    delay_ticks, ob, rv, smem_sd);
-  block_add_stats(mv.stats, dc.done, kMbProcessed, dc.failed, kMbFailed, dc.holes, kMbHoles);
-  __shared__ bool last;
-  if (threadIdx.x == 0) {
-    // the last tile's block wrote the epoch totals (gsum): release them before its ticket
-    if (t == in.tiles - 1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    last = last_block_ticket(ticket);
-    if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  __syncthreads();
-  if (last) {  // every block's records are read: the rings are consumed
-    // (reserve: the totals were built by memory-side atomics in this launch -- read and
-    // cleared the same way, not through this XCD's L2)
-    for (uint32_t s = threadIdx.x; s < S; s += kST)
-      epoch_commit(mv, s, epoch_sum(mv, gsum, 1, S, s));
-    if (threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag
-    if constexpr (RF != 0) rec8_next(in, const_cast<uint32_t*>(in.r8w), r8host, in.tiles);
-  }
-}
-
-// ---------------------------------------------------------------- arrival rings (fixed positions)
-// Arrival sharding (batches without ordered methods): tile t's messages go to
-// shard t & (S - 1), at ring offsets (t >> log S) * kSTile + (place in the
-// tile) past the epoch's tail -- FIXED positions, so there is no count pass and
-// no slot index: one enqueue pass resolves each message and writes its record
-// (a tile is one contiguous 64 KB run of its ring: whole-line stores), and the
-// drain reads the same positions in message order (whole-line loads, replies
-// coalesced).  A message with no actor here leaves a zero record (its status is
-// written by the enqueue); a tile whose run does not fit the ring's free room
-// spills whole -- the drain runs it straight from the batch, re-resolving each
-// message -- and tiles spill only as a suffix of a shard's sequence.
-__device__ __forceinline__ bool arrival_fits(const MboxView& mv, const SortIn& in, uint32_t t, uint64_t& pos0,
-                                             uint32_t tile = kSTile) {
-  const uint32_t s = t & ((1u << mv.log_s) - 1);
-  const uint64_t Q = 1ull << mv.log_q;
-  const uint64_t tl = *ctr_tail(mv, s), hd = *ctr_head(mv, s);
-  const uint64_t room = hd + Q > tl ? hd + Q - tl : 0;
-  const uint64_t off = (uint64_t)(t >> mv.log_s) * tile;
-  const uint64_t n_t = min((uint64_t)tile, (uint64_t)in.M - (uint64_t)t * tile);
-  pos0 = tl + off;
-  return off + n_t <= room;
-}
-
-template <int MODE, bool A2, bool MC>
-__global__ __launch_bounds__(kST) void mbx_arrival_enqueue_kernel(SortIn in, MboxView mv, ReplyView rv) {
-  unsigned long long n_enq = 0, n_miss = 0, n_spill = 0;
-  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
-  if (t < in.tiles) {
-    uint64_t pos0 = 0;
-    const bool fits = arrival_fits(mv, in, t, pos0);
-    const uint32_t s = t & ((1u << mv.log_s) - 1);
-    uint32_t a[kSK], mb[kSK], meth[kSK];
-    int64_t x0[kSK], x1[kSK], x2[kSK];
-    int r[kSK];
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      const int64_t i = tile_index(t, k);
-      const bool ok = i < in.M;
-      a[k] = ok ? __builtin_nontemporal_load(in.actor + i) : 0xffffffffu;
-      x0[k] = ok ? __builtin_nontemporal_load(in.a0 + i) : 0;
-      x1[k] = ok && in.a1 ? __builtin_nontemporal_load(in.a1 + i) : 0;
-      x2[k] = 0;
-      if constexpr (A2) x2[k] = ok ? __builtin_nontemporal_load(in.a2 + i) : 0;
-      meth[k] = in.method_uniform;
-      if constexpr (MC) meth[k] = ok ? (uint32_t)in.mcol[i] : 0u;
-    }
-    resolve_k<MODE>(in, a, r, mb);
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      const int64_t i = tile_index(t, k);
-      if (i >= in.M) continue;
-      const uint32_t origin = in.origin_base + (uint32_t)i;
-      const bool ok = r[k] == in.rank_self && mb[k] < kMaxMbox;
-      const uint64_t slot = slot_at(mv, s, pos0 + (uint64_t)(i - (int64_t)t * kSTile));
-      if (!ok) {
-        ++n_miss;
-        write_status(rv, origin, kStatusNoActor);
-        if (fits) *reinterpret_cast<u32x4*>(rec_a(mv, slot)) = u32x4{0u, 0u, 0u, 0u};
-        continue;
-      }
-      if (!fits) {
-        ++n_spill;
-        continue;
-      }
-      const uint32_t mt = meth[k];
-      if (mt < 128u && fits_i32(x0[k]) && fits_i32(x1[k]) && x2[k] == 0) {
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | (mt << 24), (uint32_t)x0[k], (uint32_t)x1[k]};
-      } else {
-        const uint32_t fl = x2[k] != 0 ? (uint32_t)kFlagA2 : 0u;
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | kCompactLong, (mt & 0xffffu) | (fl << 16), 0u};
-        *reinterpret_cast<u32x4*>(rec_b(mv, slot)) = u32x4{(uint32_t)x0[k], (uint32_t)((uint64_t)x0[k] >> 32),
-                                                           (uint32_t)x1[k], (uint32_t)((uint64_t)x1[k] >> 32)};
-        if (fl) mv.a2[slot] = x2[k];
-      }
-      ++n_enq;
-    }
-  }
-  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_miss, kMbNoActor, n_spill, kMbSpilled);
-}
-
-template <int FIXED, int MODE>
-__global__ __launch_bounds__(kST) void mbx_arrival_drain_kernel(MboxView mv, SortIn in, int64_t* __restrict__ state,
-                                                                uint32_t n_state, uint64_t delay_ticks, OutboxView ob,
-                                                                ReplyView rv, unsigned* __restrict__ ticket) {
-  unsigned long long done = 0, failed = 0;
-  const uint32_t S = 1u << mv.log_s;
-  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
-  if (t < in.tiles) {
-    uint64_t pos0 = 0;
-    const bool fits = arrival_fits(mv, in, t, pos0);
-    const uint32_t s = t & (S - 1);
-    SortRec x[kSK];
-    if (fits) {
-      u32x4 ha[kSK];
-#pragma unroll
-      for (int k = 0; k < kSK; ++k) {
-        const int64_t i = tile_index(t, k);
-        ha[k] = i < in.M ? *reinterpret_cast<const u32x4*>(rec_a(mv, slot_at(mv, s, pos0 + (uint64_t)(i - (int64_t)t * kSTile))))
-                         : u32x4{0u, 0u, 0u, 0u};
-      }
-#pragma unroll
-      for (int k = 0; k < kSK; ++k) {
-        u32x4 hb = {0u, 0u, 0u, 0u};
-        int64_t a2v = 0;
-        if ((ha[k].x & kCompactMark) && rec_is_long(ha[k])) {
-          const uint64_t slot = slot_at(mv, s, pos0 + (uint64_t)(tile_index(t, k) - (int64_t)t * kSTile));
-          hb = *reinterpret_cast<const u32x4*>(rec_b(mv, slot));
-          if (((ha[k].z >> 16) & kFlagA2) && mv.a2) a2v = mv.a2[slot];
-        }
-        x[k] = decode_sorted(ha[k], hb, a2v);  // a zero record (no actor): not valid
-      }
-    } else {  // the tile spilled: run it from the batch
-      uint32_t a[kSK], mb[kSK];
-      int r[kSK];
-#pragma unroll
-      for (int k = 0; k < kSK; ++k) {
-        const int64_t i = tile_index(t, k);
-        a[k] = i < in.M ? in.actor[i] : 0xffffffffu;
-      }
-      resolve_k<MODE>(in, a, r, mb);
-#pragma unroll
-      for (int k = 0; k < kSK; ++k) {
-        const int64_t i = tile_index(t, k);
-        x[k].valid = i < in.M && r[k] == in.rank_self && mb[k] < kMaxMbox;
-        if (!x[k].valid) continue;
-        x[k].mb = mb[k];
-        x[k].method = in.mcol ? (uint32_t)in.mcol[i] : in.method_uniform;
-        x[k].flags = 0;
-        x[k].a0 = in.a0[i];
-        x[k].a1 = in.a1 ? in.a1[i] : 0;
-        x[k].a2 = in.a2 ? in.a2[i] : 0;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kSK; ++k) {
-      if (!x[k].valid) continue;  // no actor: answered by the enqueue
-      MsgRecord m;
-      m.actor = x[k].mb;
-      m.method = (uint16_t)(FIXED ? FIXED : x[k].method);
-      m.flags = (uint16_t)x[k].flags;
-      m.a0 = x[k].a0, m.a1 = x[k].a1, m.a2 = x[k].a2;
-      const ReplyRecord rr = run_handler(m, state, n_state, delay_ticks, ob);
-      failed += rr.status != kStatusOk;
-      write_reply(rv, in.origin_base + (uint32_t)tile_index(t, k), rr);
-      ++done;
-    }
-  }
-  block_add_stats(mv.stats, done, kMbProcessed, failed, kMbFailed, 0, -1);
-  __shared__ bool last;
-  if (threadIdx.x == 0) last = last_block_ticket(ticket);
-  __syncthreads();
-  if (last) {  // every tile is read: each shard consumed the positions of its tiles that fit
-    for (uint32_t s = threadIdx.x; s < S; s += kST) {
-      uint64_t used = 0;
-      for (uint32_t tt = s; tt < in.tiles; tt += S) {
-        uint64_t pos0 = 0;
-        if (!arrival_fits(mv, in, tt, pos0)) break;  // the spilled suffix
-        used += min((uint64_t)kSTile, (uint64_t)in.M - (uint64_t)tt * kSTile);
-      }
-      epoch_commit(mv, s, (uint32_t)used);
-    }
-  }
-}
-
-// Arrival rings, enqueue and drain in ONE launch.  Block t writes tile t's records
-// into its run of ring t & (S - 1) (the positions mbx_arrival_enqueue_kernel uses) and,
-// after a block barrier, drains that run: wave w consumes the records wave w ^ 4 wrote
-// -- read back from the ring, decoded, its handler run -- so the ring is the hand-off
-// between the block's waves, as it is between the two kernels of the general form (no
-// grid-wide phase is needed: an arrival run belongs to one tile).  Uniform batches of at
-// most two arguments; MODE 3 (rank byte routes, stateless methods) carries actor ids.
-//
-// Record format per WAVE (its producer decides with one ballot and tells its consumer
-// through LDS, across the barrier the hand-off needs anyway; allow8 -- batches past 512
-// tiles, the rule of the sort's 8-B records): 8 B {mailbox 24 | zigzag
-// a0 20 | zigzag a1 20} when every message of the wave fits, in the first half of the
-// wave's own 512 slots (message j in half j & 1 of slot j / 2 of that range: formats
-// never overlap), else the 16-B compact form (32-B long form for a value past 32 bits).
-constexpr int kArr8Mb = 24, kArr8Arg = 20;
-constexpr uint64_t kArr8Null = ~0ull;  // a slot of no actor (mailbox 2^24 - 1 never fits the 8-B form)
-__device__ __forceinline__ bool arr8_fits(uint32_t mb, int64_t x0, int64_t x1) {
-  const uint64_t z0 = ((uint64_t)x0 << 1) ^ (uint64_t)(x0 >> 63), z1 = ((uint64_t)x1 << 1) ^ (uint64_t)(x1 >> 63);
-  return mb < (1u << kArr8Mb) - 1u && (z0 >> kArr8Arg) == 0 && (z1 >> kArr8Arg) == 0;
-}
-template <int SK>
-__device__ __forceinline__ uint64_t arr8_cell(const MboxView& mv, uint32_t s, uint64_t pos0, uint32_t j) {
-  constexpr uint32_t run = SK * kWave;  // a wave's run of the tile
-  return 2 * slot_at(mv, s, pos0 + (j & ~(run - 1)) + ((j & (run - 1)) >> 1)) + (j & 1);
-}
-// SK messages per thread: kSK (4096-message tiles), or 2 (1024) for batches of up to 512
-// 4096-message tiles -- one 8-wave block per CU at 1 Mi messages hid too little latency
-template <int MODE, int FIXED, int SK = kSK>
-__global__ __launch_bounds__(kST) void mbx_arrival_fused_kernel(SortIn in, MboxView mv, int64_t* __restrict__ state,
-                                                                uint32_t n_state, uint64_t delay_ticks, OutboxView ob,
-                                                                ReplyView rv, unsigned* __restrict__ ticket,
-                                                                bool allow8) {
-  __shared__ uint32_t wave_rec8[kST / kWave];
-  extern __shared__ __align__(16) unsigned char smem_af[];  // MODE 4: the presence map
-  uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_af);
-  if constexpr (MODE == 4) {
-    stage_pres(in, lpres);
-    __syncthreads();
-  }
-  unsigned long long n_enq = 0, n_miss = 0, n_spill = 0, done = 0, failed = 0;
-  const uint32_t S = 1u << mv.log_s;
-  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
-  const unsigned w = threadIdx.x / kWave;
-  if (t < in.tiles) {
-    uint64_t pos0 = 0;
-    constexpr uint32_t kTile = kST * SK;
-    const bool fits = arrival_fits(mv, in, t, pos0, kTile);
-    const uint32_t s = t & (S - 1);
-    uint32_t a[SK], mb[SK];
-    int64_t x0[SK], x1[SK];
-    int r[SK];
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      const int64_t i = tile_index<SK>(t, k);
-      const bool ok = i < in.M;
-      a[k] = ok ? __builtin_nontemporal_load(in.actor + i) : 0xffffffffu;
-      x0[k] = ok ? __builtin_nontemporal_load(in.a0 + i) : 0;
-      x1[k] = ok && in.a1 ? __builtin_nontemporal_load(in.a1 + i) : 0;
-    }
-    if constexpr (MODE == 4) resolve_pres<SK>(in, lpres, a, r, mb);
-    else resolve_k<MODE, SK>(in, a, r, mb);
-    bool live[SK];
-    bool narrow = allow8 && mv.planar != 0;
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      live[k] = tile_index<SK>(t, k) < in.M && r[k] == in.rank_self && mb[k] < kMaxMbox;
-      if (live[k] && !arr8_fits(mb[k], x0[k], x1[k])) narrow = false;
-    }
-    const bool rec8 = __ballot(!narrow) == 0;  // (wave-uniform)
-    if (lane_id() == 0) wave_rec8[w] = rec8;
-    uint64_t* cells = reinterpret_cast<uint64_t*>(mv.rec);
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {  // enqueue: the tile's records at their fixed ring positions
-      const int64_t i = tile_index<SK>(t, k);
-      if (i >= in.M) continue;
-      const uint32_t origin = in.origin_base + (uint32_t)i;
-      const uint32_t j = (uint32_t)(i - (int64_t)t * kTile);
-      const uint64_t slot = slot_at(mv, s, pos0 + j);
-      if (!live[k]) {
-        ++n_miss;
-        write_status(rv, origin, kStatusNoActor);
-        if (fits && rec8) cells[arr8_cell<SK>(mv, s, pos0, j)] = kArr8Null;
-        else if (fits) *reinterpret_cast<u32x4*>(rec_a(mv, slot)) = u32x4{0u, 0u, 0u, 0u};
-        continue;
-      }
-      if (!fits) {  // the tile spilled: its messages run from the registers below
-        ++n_spill;
-        continue;
-      }
-      const uint32_t mt = in.method_uniform;
-      if (rec8) {
-        const uint64_t z0 = ((uint64_t)x0[k] << 1) ^ (uint64_t)(x0[k] >> 63);
-        const uint64_t z1 = ((uint64_t)x1[k] << 1) ^ (uint64_t)(x1[k] >> 63);
-        cells[arr8_cell<SK>(mv, s, pos0, j)] = (uint64_t)mb[k] | (z0 << kArr8Mb) | (z1 << (kArr8Mb + kArr8Arg));
-      } else if (mt < 128u && fits_i32(x0[k]) && fits_i32(x1[k])) {
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | (mt << 24), (uint32_t)x0[k], (uint32_t)x1[k]};
-      } else {
-        *reinterpret_cast<u32x4*>(rec_a(mv, slot)) =
-            u32x4{origin | kCompactMark, mb[k] | kCompactLong, mt & 0xffffu, 0u};
-        *reinterpret_cast<u32x4*>(rec_b(mv, slot)) = u32x4{(uint32_t)x0[k], (uint32_t)((uint64_t)x0[k] >> 32),
-                                                           (uint32_t)x1[k], (uint32_t)((uint64_t)x1[k] >> 32)};
-      }
-      ++n_enq;
-    }
-    __syncthreads();  // the run is in the ring: drain it
-    const uint32_t w2 = w ^ 4u;  // (the wave whose records this one consumes)
-    const bool rec8_2 = wave_rec8[w2] != 0;
-#pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      SortRec x;
-      int64_t i;
-      if (fits) {  // wave w2's k-th record of this lane
-        const uint32_t j = w2 * (SK * kWave) + (uint32_t)k * kWave + lane_id();
-        i = (int64_t)t * kTile + j;
-        if (i >= in.M) continue;
-        if (rec8_2) {
-          const uint64_t c = cells[arr8_cell<SK>(mv, s, pos0, j)];
-          if (c == kArr8Null) continue;  // no actor: answered by the enqueue
-          x.valid = true, x.method = in.method_uniform, x.flags = 0, x.a2 = 0;
-          x.mb = (uint32_t)(c & ((1u << kArr8Mb) - 1));
-          const uint64_t z0 = (c >> kArr8Mb) & ((1ull << kArr8Arg) - 1), z1 = c >> (kArr8Mb + kArr8Arg);
-          x.a0 = (int64_t)(z0 >> 1) ^ -(int64_t)(z0 & 1);
-          x.a1 = (int64_t)(z1 >> 1) ^ -(int64_t)(z1 & 1);
-        } else {
-          const uint64_t slot = slot_at(mv, s, pos0 + j);
-          const u32x4 ha = *reinterpret_cast<const u32x4*>(rec_a(mv, slot));
-          const u32x4 hb = rec_is_long(ha) ? *reinterpret_cast<const u32x4*>(rec_b(mv, slot)) : u32x4{0u, 0u, 0u, 0u};
-          x = decode_sorted(ha, hb, 0);  // a zero record (no actor): not valid
-          if (!x.valid) continue;
-        }
-      } else {  // a spilled tile: this thread's own messages, from its registers
-        if (!live[k]) continue;  // (no actor: answered above)
-        i = tile_index<SK>(t, k);
-        x.valid = true, x.mb = mb[k], x.method = in.method_uniform, x.flags = 0;
-        x.a0 = x0[k], x.a1 = x1[k], x.a2 = 0;
-      }
-      MsgRecord m;
-      m.actor = x.mb;
-      m.method = (uint16_t)(FIXED ? FIXED : x.method);
-      m.flags = (uint16_t)x.flags;
-      m.a0 = x.a0, m.a1 = x.a1, m.a2 = 0;
-      const ReplyRecord rr = run_handler(m, state, n_state, delay_ticks, ob);
-      failed += rr.status != kStatusOk;
-      write_reply(rv, in.origin_base + (uint32_t)i, rr);
-      ++done;
-    }
-  }
-  block_add_stats(mv.stats, n_enq, kMbEnqueued, n_miss, kMbNoActor, n_spill, kMbSpilled);
-  __syncthreads();  // block_add_stats' LDS partials are reused
-  block_add_stats(mv.stats, done, kMbProcessed, failed, kMbFailed, 0, -1);
-  __shared__ bool last;
-  if (threadIdx.x == 0) last = last_block_ticket(ticket);
-  __syncthreads();
-  if (last) {  // every tile is read: each shard consumed the positions of its tiles that fit
-    for (uint32_t sh = threadIdx.x; sh < S; sh += kST) {
-      uint64_t used = 0;
-      for (uint32_t tt = sh; tt < in.tiles; tt += S) {
-        uint64_t p0 = 0;
-        if (!arrival_fits(mv, in, tt, p0, kST * SK)) break;  // the spilled suffix
-        used += min((uint64_t)(kST * SK), (uint64_t)in.M - (uint64_t)tt * (kST * SK));
-      }
-      epoch_commit(mv, sh, (uint32_t)used);
-    }
-  }
-}
-
-// ---------------------------------------------------------------- K3s ordered drain
-// One block owns shard s: its actors' state is staged in LDS (when it fits), and
-// the shard's records are taken in windows of kOrdWin in ring order.  A window
-// is sorted stably in LDS into kOrdThreads bins by actor (bin = local actor index
-// mod bins), then thread b runs bin b's records one at a time in ring order: an
-// actor's messages run serially and in FIFO order, distinct bins in parallel.
-// Every method of the shard runs here (so a batch mixing ordered and other
-// methods keeps per-actor FIFO across all of them).  Replies are staged at the
-// records' ring slots (a window's slots are contiguous: whole lines), and
-// mbx_complete_kernel gathers them into message order.
-// A12: the batch carries a second / third argument column.  Without them (a
-// one-argument ordered method, e.g. SeqFold) the window's a1 / a2 arrays are not
-// allocated: 68 instead of 100 KB of LDS, so two drain blocks fit a CU.
-template <bool A12, int OK = kOrdK>
-struct OrdLds {
-  static constexpr int kWin = kOrdThreads * OK;
-  uint32_t wcnt[kOrdWaves][kOrdThreads];  // per-wave bin counts -> offsets
-  uint32_t bstart[kOrdThreads];
-  uint32_t bcount[kOrdThreads];
-  uint32_t wsum[kOrdWaves];
-  uint32_t slot[kWin];
-  uint32_t act[kWin];  // actor index for the handler (LDS-local or global mailbox)
-  uint32_t meth[kWin];  // method | flags << 16
-  uint32_t orig[kWin];  // origin: the completion's place for the reply
-  int64_t a0[kWin], a1[A12 ? kWin : 2], a2[A12 ? kWin : 2];
+struct VariantName {
+  int family;
+  uint32_t key;
+  const char* name;
 };
 
-// OK: records per thread per window (window = 512 * OK records: OK = 8 for one-argument batches).
-// FIXED = kSeqFold: a uniform SeqFold batch.  With every actor of the shard in its
-// own bin (at most kOrdThreads of them, state staged), thread b IS actor b's
-// consumer for the whole Send: its state stays in a register and each record is
-// one fold (reply = the state before, state = state * kFoldMul + a0) -- no handler
-// switch, no LDS state round trip per message.
-// R8: the sort wrote 8-B records (a uniform one-argument batch): each carries its
-// place in its tile (12 bits), the mailbox and the zigzag argument at the widths
-// *r8w; mbx_rec8_next_kernel derives the next Send's widths after the drain.
-struct R8Args {
-  const uint32_t* r8w = nullptr;  // this Send's widths (the sort's)
-  uint32_t method = 0;            // the batch's uniform method
-  const int64_t* esc = nullptr;   // escape records' {a0, mailbox}, by ring slot (SortIn::r8esc)
-};
-__device__ __forceinline__ SortRec decode_rec8_ord(uint64_t r, uint32_t w8, uint32_t method, const int64_t* esc,
-                                                   uint64_t slot) {
-  const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu, w1 = (w8 >> 16) & 0xffu;
-  SortRec x;
-  x.valid = true;
-  x.origin = (uint32_t)(r & (kSTile - 1));  // the place in the tile
-  x.method = method;
-  x.flags = 0;
-  x.a2 = 0;
-  if (r >> 63) {  // escape record (one-argument batches leave the top bit of a record zero)
-    const u32x4 e = *reinterpret_cast<const u32x4*>(esc + 2 * slot);
-    x.a0 = (int64_t)(((uint64_t)e.y << 32) | e.x);
-    x.mb = e.z;
-    x.a1 = 0;
-    return x;
-  }
-  x.mb = (uint32_t)((r >> 12) & ((1ull << wm) - 1));
-  const uint64_t z0 = (r >> (12 + wm)) & ((1ull << w0) - 1), z1 = (r >> (12 + wm + w0)) & ((1ull << w1) - 1);
-  x.a0 = (int64_t)(z0 >> 1) ^ -(int64_t)(z0 & 1);
-  x.a1 = (int64_t)(z1 >> 1) ^ -(int64_t)(z1 & 1);
-  return x;
+namespace {  // (per TU: a table's once-flag is its own)
+template <class Fn, size_t N>
+Fn* variant(const Variant<Fn> (&t)[N], uint32_t key) {
+  for (const Variant<Fn>& r : t)
+    if (r.key == key) return r.fn;
+  throw std::logic_error(std::string("mailbox send: no variant of ") + t[0].name + " for key " + std::to_string(key));
 }
-
-// A window's records (their first 16 B; R8: the 8-B record), wave w's positions.
-template <bool R8, int OK>
-__device__ __forceinline__ void ord_load_win(const MboxView& mv, uint64_t wa, uint64_t n_end, uint64_t sbase,
-                                             uint64_t rot, uint64_t qmask, unsigned w, unsigned lane,
-                                             typename std::conditional<R8, uint64_t, u32x4>::type (&h)[OK]) {
-#pragma unroll
-  for (int k = 0; k < OK; ++k) {
-    const uint64_t q = wa + (uint64_t)w * (kWave * OK) + (uint64_t)k * kWave + lane;
-    const uint64_t sl = sbase | ((q + rot) & qmask);
-    const bool in = q < n_end && q < wa + (kOrdThreads * OK);
-    if constexpr (R8) h[k] = in ? reinterpret_cast<const uint64_t*>(mv.rec)[sl] : 0ull;
-    else h[k] = in ? *reinterpret_cast<const u32x4*>(rec_a(mv, sl)) : u32x4{0u, 0u, 0u, 0u};
-  }
+// once per process, before the first launch that may need it
+template <class Fn, size_t N>
+void variants_allow_lds(const Variant<Fn> (&t)[N]) {
+  static bool done = false;
+  if (done) return;
+  for (const Variant<Fn>& r : t)
+    if (r.max_lds)
+      PT_HIP_CHECK(hipFuncSetAttribute((const void*)r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.max_lds));
+  done = true;
 }
-
-// (one block per CU whatever its registers -- the window's LDS -- so the register
-// budget is that of 2 waves per SIMD: no spill for the prefetched window)
-template <bool A12, int OK = kOrdK, int FIXED = 0, bool PF = false, bool R8 = false>
-__global__ __launch_bounds__(kOrdThreads) __attribute__((amdgpu_waves_per_eu(1, 2))) void mbx_drain_ordered_kernel(MboxView mv, uint32_t* __restrict__ gsum,
-                                                                        uint32_t ngroups, int64_t* __restrict__ state,
-                                                                        uint32_t n_state, uint64_t delay_ticks,
-                                                                        OutboxView ob, u32x4* __restrict__ srep,
-                                                                        uint32_t origin_base, R8Args r8) {
-  extern __shared__ __align__(16) unsigned char smem_ord[];
-  OrdLds<A12, OK>& L = *reinterpret_cast<OrdLds<A12, OK>*>(smem_ord);
-  int64_t* st_lds = reinterpret_cast<int64_t*>(smem_ord + sizeof(OrdLds<A12, OK>));
-  const uint32_t s = blockIdx.x;
-  const uint32_t S = 1u << mv.log_s;
-  const uint64_t Q = 1ull << mv.log_q;
-  const unsigned w = threadIdx.x / kWave, lane = lane_id();
-  __shared__ uint32_t tot_s;
-  if (threadIdx.x == 0) tot_s = epoch_total(gsum, ngroups, S, s, true);
-  const uint64_t lo = *ctr_tail(mv, s), hd = *ctr_head(mv, s);
-  const uint64_t free = hd + Q > lo ? hd + Q - lo : 0;
-  // this shard's actors are mailboxes s, s + S, s + 2S, ...: local index j = mb >> log_s
-  const uint32_t n_loc = (state && s < n_state) ? (n_state - 1 - s) / S + 1 : 0;
-  const bool in_lds = state && n_loc <= kOrdStateMax;
-  if (in_lds)
-    for (uint32_t j = threadIdx.x; j < n_loc; j += kOrdThreads) st_lds[j] = state[s + (uint64_t)j * S];
-  __syncthreads();
-  const bool reg = FIXED == kSeqFold && in_lds && n_loc <= (uint32_t)kOrdThreads;  // actor b's state in thread b
-  uint64_t sreg = reg && threadIdx.x < n_loc ? (uint64_t)st_lds[threadIdx.x] : 0ull;
-  const uint32_t tot = tot_s;
-  const uint64_t n = tot < free ? tot : free;
-  const uint64_t sbase = (uint64_t)s << mv.log_q, qmask = Q - 1, rot = shard_rot(mv, s);  // slot_at, hoisted
-  unsigned long long done = 0, failed = 0, holes = 0, serial = 0;
-  // PF (the fold: the next window's records (their first 16 B) are loaded
-  // while this one is binned and run -- one block per CU (the LDS), so the registers are
-  // there.  (Round 3, with the handler switch's register file: measured no faster, 188 ->
-  // 200 us, and spilled to scratch.)
-  const uint64_t n_end = lo + n;
-  using RawT = typename std::conditional<R8, uint64_t, u32x4>::type;  // a record's first (R8: only) word
-  const uint32_t w8 = R8 ? *r8.r8w : 0u;
-  RawT cur[PF ? OK : 1];
-  if constexpr (PF) {
-    if (lo < n_end) ord_load_win<R8, OK>(mv, lo, n_end, sbase, rot, qmask, w, lane, cur);
-  }
-  for (uint64_t w0 = lo; w0 < lo + n; w0 += (kOrdThreads * OK)) {
-    const uint64_t w1 = lo + n < w0 + (kOrdThreads * OK) ? lo + n : w0 + (kOrdThreads * OK);
-    for (uint32_t b = lane; b < kOrdThreads; b += kWave) L.wcnt[w][b] = 0;
-    SortRec x[OK];
-    uint32_t bin[OK], wr[OK];
-    uint64_t slot[OK];
-    RawT nxt[PF ? OK : 1];
-    if constexpr (PF) {
-      if (w0 + (kOrdThreads * OK) < n_end)
-        ord_load_win<R8, OK>(mv, w0 + (kOrdThreads * OK), n_end, sbase, rot, qmask, w, lane, nxt);
-    }
-#pragma unroll
-    for (int k = 0; k < OK; ++k) {  // wave w owns window positions [w * 64K, (w+1) * 64K)
-      const uint64_t q = w0 + (uint64_t)w * (kWave * OK) + (uint64_t)k * kWave + lane;
-      slot[k] = sbase | ((q + rot) & qmask);
-      if (q < w1) {
-        if constexpr (R8) {
-          x[k] = decode_rec8_ord(PF ? (uint64_t)cur[k] : reinterpret_cast<const uint64_t*>(mv.rec)[slot[k]], w8,
-                                 r8.method, r8.esc, slot[k]);
-        } else if constexpr (PF) {
-          u32x4 hb = {0u, 0u, 0u, 0u};
-          int64_t a2v = 0;
-          if (rec_is_long(cur[k])) {
-            hb = *reinterpret_cast<const u32x4*>(rec_b(mv, slot[k]));
-            if (((cur[k].z >> 16) & kFlagA2) && mv.a2) a2v = mv.a2[slot[k]];
-          }
-          x[k] = decode_sorted(cur[k], hb, a2v);
-        } else {
-          x[k] = load_sorted(mv, slot[k]);
-        }
-        if (!x[k].valid) ++holes;
-      } else {
-        x[k].valid = false;
-      }
-    }
-    if constexpr (PF) {
-#pragma unroll
-      for (int k = 0; k < OK; ++k) cur[k] = nxt[k];
-    }
-#pragma unroll
-    for (int k = 0; k < OK; ++k) {
-      bin[k] = (x[k].mb >> mv.log_s) & (kOrdThreads - 1);
-      const uint64_t peers = match_bits(bin[k], 9, __ballot(x[k].valid));
-      const unsigned below = mbcnt64(peers);
-      const int leader = peers ? __builtin_ctzll(peers) : 0;
-      unsigned old = 0;
-      if (x[k].valid && below == 0) {
-        old = L.wcnt[w][bin[k]];
-        L.wcnt[w][bin[k]] = old + (unsigned)__popcll(peers);
-      }
-      wr[k] = (unsigned)__shfl((int)old, leader) + below;
-    }
-    __syncthreads();
-    {  // bin totals and wave offsets (thread b owns bin b), then an exclusive scan over bins
-      const unsigned b = threadIdx.x;
-      unsigned r = 0;
-#pragma unroll
-      for (int ww = 0; ww < kOrdWaves; ++ww) {
-        const unsigned c = L.wcnt[ww][b];
-        L.wcnt[ww][b] = r;
-        r += c;
-      }
-      L.bcount[b] = r;
-      const unsigned inc = wave_incl_scan(r);
-      if (lane == kWave - 1) L.wsum[w] = inc;
-      __syncthreads();
-      unsigned off = inc - r;
-      for (unsigned ww = 0; ww < w; ++ww) off += L.wsum[ww];
-      L.bstart[b] = off;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < OK; ++k) {
-      if (!x[k].valid) continue;
-      const unsigned d = L.bstart[bin[k]] + L.wcnt[w][bin[k]] + wr[k];
-      L.slot[d] = (uint32_t)slot[k];
-      L.act[d] = in_lds ? (x[k].mb >> mv.log_s) : x[k].mb;
-      if (!reg) L.meth[d] = x[k].method | (x[k].flags << 16);
-      // the message's place in its tile (the completion reads the tile's runs)
-      L.orig[d] = R8 ? x[k].origin : ((x[k].origin - origin_base) & (uint32_t)(kSTile - 1));
-      L.a0[d] = x[k].a0;
-      if constexpr (A12) {
-        L.a1[d] = x[k].a1;
-        L.a2[d] = x[k].a2;
-      }
-    }
-    __syncthreads();
-    if (reg) {  // uniform SeqFold, one actor per bin: the folds in a register
-      const unsigned b = threadIdx.x, e = L.bstart[b] + L.bcount[b];
-      if (L.bcount[b] > 1) serial += L.bcount[b] - 1;
-      for (unsigned d = L.bstart[b]; d < e; ++d) {
-        const uint64_t prev = sreg;
-        uint32_t st = kStatusOk;
-        if (L.act[d] == b && b < n_loc) {
-          sreg = prev * kFoldMul + (uint64_t)L.a0[d];
-        } else {  // a mailbox past the state (routed here by a stale registry entry)
-          st = kStatusNoActor;
-          ++failed;
-        }
-        const uint64_t v = st == kStatusOk ? prev : 0ull;
-        srep[L.slot[d]] = u32x4{(uint32_t)v, (uint32_t)(v >> 32), st, L.orig[d]};
-        ++done;
-      }
-    } else {  // this thread's bin, serially in ring order
-      const unsigned b = threadIdx.x, e = L.bstart[b] + L.bcount[b];
-      if (L.bcount[b] > 1) serial += L.bcount[b] - 1;  // records that waited behind their bin's earlier ones
-      int64_t* st = in_lds ? st_lds : state;
-      const uint32_t nst = in_lds ? n_loc : n_state;
-      for (unsigned d = L.bstart[b]; d < e; ++d) {
-        MsgRecord m;
-        m.actor = L.act[d];
-        m.method = (uint16_t)(L.meth[d] & 0xffffu);
-        m.flags = (uint16_t)(L.meth[d] >> 16);
-        m.a0 = L.a0[d];
-        m.a1 = A12 ? L.a1[d] : 0;
-        m.a2 = A12 ? L.a2[d] : 0;
-        const ReplyRecord rr = run_handler(m, st, nst, delay_ticks, ob, true);
-        failed += rr.status != kStatusOk;
-        srep[L.slot[d]] = u32x4{(uint32_t)rr.value, (uint32_t)((uint64_t)rr.value >> 32), (uint32_t)rr.status, L.orig[d]};
-        ++done;
-        if (!in_lds) vm_drain();  // global state: this store lands before the bin's next load
-      }
-    }
-    __syncthreads();  // the window's LDS is reused
-  }
-  if (reg && threadIdx.x < n_loc) st_lds[threadIdx.x] = (int64_t)sreg;
-  if (reg) __syncthreads();
-  if (in_lds)
-    for (uint32_t j = threadIdx.x; j < n_loc; j += kOrdThreads) state[s + (uint64_t)j * S] = st_lds[j];
-  block_add_stats(mv.stats, done, kMbProcessed, failed, kMbFailed, holes, kMbHoles);
-  __syncthreads();  // block_add_stats' LDS partials are reused
-  block_add_stats(mv.stats, serial, kMbSerial, 0, -1, 0, -1);
-  if (threadIdx.x == 0) epoch_commit(mv, s, tot);
+template <class Fn, size_t N>
+void variant_names(int family, const Variant<Fn> (&t)[N], std::vector<VariantName>& out) {
+  for (const Variant<Fn>& r : t) out.push_back({family, r.key, r.name});
 }
+}  // namespace
 
-// The next Send's 8-B field widths after an ordered 8-B-record Send (one block, launched
-// after the ordered drain: every block of it has decoded with this Send's widths).
-template <int = 0>  // (a template: the header is compiled into every launcher TU that uses it)
-__global__ __launch_bounds__(256) void mbx_rec8_next_kernel(const uint32_t* __restrict__ r8max,
-                                                            uint32_t* __restrict__ r8w, uint32_t* __restrict__ host,
-                                                            uint32_t tiles) {
-  rec8_next_from(r8max, r8w, host, tiles);
-}
-
-template <int = 0>
-__global__ __launch_bounds__(kST) void mbx_complete_ring_kernel(SortIn in, MboxView mv,
-                                                                const uint32_t* __restrict__ tinfo,
-                                                                const u32x4* __restrict__ srep, ReplyView rv,
-                                                                unsigned* __restrict__ tctr) {
-  extern __shared__ __align__(16) unsigned char smem_cr[];
-  if (blockIdx.x == 0 && threadIdx.x == 0) tctr[1] += 1u;  // the next Send's one-pass epoch tag (the sort is done)
-  const uint32_t S = 1u << mv.log_s;
-  int64_t* sval = reinterpret_cast<int64_t*>(smem_cr);
-  RunLds<uint16_t> L;
-  L.bias = reinterpret_cast<uint32_t*>(sval + kSTile);
-  L.excl = L.bias + S;
-  L.owner = reinterpret_cast<uint16_t*>(L.excl + S);
-  uint8_t* sst = reinterpret_cast<uint8_t*>(L.owner + kSTile);
-  const uint32_t t = virt_block(blockIdx.x, gridDim.x);
-  if (t >= in.tiles) return;
-  const uint64_t i0 = (uint64_t)t * kSTile;
-  const uint32_t n_t = (uint32_t)min((uint64_t)kSTile, (uint64_t)in.M - i0);
-  for (uint32_t j = threadIdx.x; j < kSTile; j += kST) sst[j] = kAbsent;
-  int spill = 0;
-  const uint32_t T = load_tile_runs(mv, tinfo, t, L, spill);
-  const uint64_t qmask = (1ull << mv.log_q) - 1;
-  u32x4 r[kSK];
-#pragma unroll
-  for (int k = 0; k < kSK; ++k) {
-    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
-    if (j < T) {
-      const uint32_t s = L.owner[j];
-      // (read once: non-temporal -- SeqFold 25.64-25.87 vs 25.22-25.57 G and 25.74-25.85 vs
-      // 25.35-25.52 G in two sessions, alternated; profiles/r6_small_sends.md)
-      r[k] = __builtin_nontemporal_load(srep + (((uint64_t)s << mv.log_q) | ((L.bias[s] + j) & qmask)));
-    } else {
-      r[k] = u32x4{0u, 0u, 0u, 0xffffffffu};
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kSK; ++k) {
-    const uint32_t local = r[k].w;  // the place in the tile (the drains write it; 0xffffffff: none)
-    if (local < n_t) {
-      sval[local] = (int64_t)(((uint64_t)r[k].y << 32) | r[k].x);
-      sst[local] = (uint8_t)r[k].z;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kSK; ++k) {
-    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
-    if (j < n_t && sst[j] != kAbsent) put_reply(rv, in.origin_base + (uint32_t)(i0 + j), sval[j], sst[j]);
-  }
-}
-
-// ---------------------------------------------------------------- host
-// The fused sort + drain kernel: slower than the two kernels for large batches once the sort
-// reserves its runs (8 Mi: 149 vs 95 + 39 us; its register file halves the drain's occupancy),
-// faster for small ones, where a launch and a kernel boundary weigh more (1 Mi bench step: 5-7 %
-// in three sessions).  Fused up to 512 tiles (2 Mi messages); tune mbox_fused=1 / 0 forces it.
-
-// ---------------------------------------------------------------- out-of-TU launchers
-// The fused one-pass sort + ring-order drain of a stateless Send (mailbox_sort_fused.hip).
-struct MbxFusedLaunch {
-  SortIn in;
-  MboxView mv;
-  unsigned long long* desc;
-  unsigned* tctr;
-  uint32_t *gsum, *sidx, *tinfo, *rw;
-  ReplyView rv;
+// ---------------------------------------------------------------- launchers
+// What every launcher takes besides the plan, the batch and the ring view: the Send's
+// workspaces (Mailboxes::sort_ws) and what the handlers run on.
+struct HandlerArgs {
   int64_t* state;
   uint32_t n_state;
   uint64_t delay_ticks;
   OutboxView ob;
-  unsigned* ticket;
-  bool reserve;
-  uint32_t* r8host;
-  size_t lds;
-  hipStream_t st;
-  int rf, mode;
-  bool fixed_mul, rank_route, a2, mcol;
-};
-void mbx_launch_fused(const MbxFusedLaunch& f);
-void mbx_launch_fused_dir(const MbxFusedLaunch& f);    // route modes 1, 3
-void mbx_launch_fused_other(const MbxFusedLaunch& f);  // route modes 0, 2
-
-// The ordered drain + the ring-order completion of an ordered Send (mailbox_sort_ordered.hip).
-struct MbxOrderedLaunch {
-  SortIn in;
-  MboxView mv;
-  uint32_t* gsum;
-  uint32_t ngroups;
-  int64_t* state;
-  uint32_t n_state;
-  uint64_t delay_ticks;
-  OutboxView ob;
-  u32x4* stage_rep;
-  uint32_t origin_base;
-  uint32_t Sv;
-  bool r8_on, a12, fold;
-  R8Args r8a;
-  uint32_t *r8max, *r8w, *r8host;
-  uint32_t* tinfo;
   ReplyView rv;
-  unsigned* tctr;
-  uint32_t tile_grid;
-  hipStream_t st;
 };
-void mbx_launch_ordered(const MbxOrderedLaunch& o);
+// mailbox_sort_fused.hip (route modes 1 and 3) and mailbox_sort_fused_other.hip (0 and 2)
+void mbx_launch_fused(const SortPlan& p, const SortIn& in, const MboxView& mv, const SortWs& ws, const HandlerArgs& h,
+                      hipStream_t st);
+void mbx_launch_fused_other(const SortPlan& p, const SortIn& in, const MboxView& mv, const SortWs& ws,
+                            const HandlerArgs& h, hipStream_t st);
+// mailbox_sort_ordered.hip: the ordered drain + the ring-order completion
+void mbx_launch_ordered(const SortPlan& p, const SortIn& in, const MboxView& mv, const SortWs& ws,
+                        const HandlerArgs& h, hipStream_t st);
+// mailbox_sort_arrival.hip: a Send on arrival rings, whole
+void mbx_launch_arrival(const SortPlan& p, const SortIn& in, const MboxView& mv, const SortWs& ws,
+                        const HandlerArgs& h, hipStream_t st);
+// each TU's rows (_hip.mailbox_variants)
+void mbx_fused_variants(std::vector<VariantName>& out);
+void mbx_fused_other_variants(std::vector<VariantName>& out);
+void mbx_ordered_variants(std::vector<VariantName>& out);
+void mbx_arrival_variants(std::vector<VariantName>& out);
 
 }  // namespace ptype

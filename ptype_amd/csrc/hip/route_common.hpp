@@ -4,6 +4,7 @@
 // (batch.hip) and the single-pass look-back route (route_fused.hip).
 #pragma once
 #include "common.hpp"
+#include "sort_limits.hpp"
 
 namespace ptype {
 
@@ -12,7 +13,6 @@ constexpr int kRouteThreads = 256;
 constexpr int kScatterItems = 2;
 constexpr int kScatterTile = kRouteThreads * kScatterItems;
 constexpr uint32_t kRouteNoActor = 0xffu;  // route word rank byte for a registry miss
-constexpr uint32_t kMaxMbox = 1u << 24;
 
 // Resolve `key` against one probe group held in registers.  Written with named
 // registers and selects, not an indexed array + early return: that form made

@@ -10,6 +10,7 @@
 // _hip.set_tune) or the environment, PTYPE_TUNE="key=value,key=value" (tests and
 // the profiling tools).  The table is re-read when PTYPE_TUNE changes, and each
 // engine reads it when it is built or per Send -- never per kernel.
+// The mbox_* switches are read in one place, plan_sorted (mailbox_plan.hpp).
 //
 //   key               default  meaning
 //   mbox_fused        -1       stateless world-1 mailbox Sends: fused sort + drain kernel

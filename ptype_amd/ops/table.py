@@ -83,7 +83,7 @@ class RegistryTable:
         self.affine = 0  # W when the last build verified the rule for every id of the range
         self._astats = None
         self._dir_dirty = True
-        # route mode 4 (csrc/hip/mailbox_sort_dev.hpp): the directory folded into 2 bits
+        # route mode 4 (csrc/hip/mailbox_plan.hpp; folded by mailbox_sort.hip): the directory folded into 2 bits
         # per id for rank `presence_rank` -- here / probe the table / not here -- rebuilt
         # with the directory, for directories that fit a sort block's LDS (<= 2^18 ids)
         self.presence = None
