@@ -202,7 +202,7 @@ class Client:
         return self._c.go(serviceMethod, args, done)
 
     def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None,
-             cache: bool | None = None, **kw):
+             cache: bool | None = None, gather=None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -254,7 +254,19 @@ class Client:
         ``Stats()["runtime"]["cache"]`` counts messages, hits and misses sent.  The
         cache belongs to the process's runtime: cached Sends must all be issued on one
         stream, and clients of different replicated services (different routers)
-        that alternate on it clear it on every Send."""
+        that alternate on it clear it on every Send.
+
+        ``gather``: the gather half of a scatter-gather (the optimus coordinator's
+        ``watchReplies``) -- an ``ops.gather.Gather(group, groups, op, sentinel)`` over
+        this batch folds the replies into one result per group on the device: ``sum``,
+        ``min``, ``max`` or ``first_ne`` over the ``STATUS_OK`` replies of each group, with
+        the group's first error in message order (ops/gather.py).  The return value
+        stays ``(value, status)`` per message; the results are the object's tensors
+        (``value``, ``status``, ``n_ok``, ``count``, ``bad_row``, ``oob``), valid in stream
+        order after the Send and overwritten by the next Send that carries it.  It
+        runs once, on the full batch's final replies (after coalescing, the cache,
+        retries and overflow re-sends), costs two kernel launches and no host read,
+        and like an accounted Send never defers its overflow re-sends."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
@@ -263,6 +275,8 @@ class Client:
             kw.update(coalesce=bool(coalesce))
         if cache is not None:
             kw.update(cache=bool(cache))
+        if gather is not None:
+            kw.update(gather=gather)
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

@@ -13,6 +13,7 @@
 #include "engine.hpp"
 #include "exchange_sorted.hpp"
 #include "ipc_comm.hpp"
+#include "gather.hpp"
 #include "ledger.hpp"
 #include "mailbox.hpp"
 #include "reply_cache.hpp"
@@ -126,6 +127,9 @@ void launch_reply_cache_insert(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintpt
 void launch_reply_cache_insert_phase(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t,
                                      uintptr_t, uintptr_t, int, uint32_t, uint32_t, int, uintptr_t);
 void launch_reply_cache_clear(uintptr_t, int, uintptr_t);
+int64_t reply_gather_tile();
+void launch_reply_gather(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int, uintptr_t, uintptr_t, uintptr_t,
+                         uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -412,6 +416,25 @@ PYBIND11_MODULE(_hip, m) {
         "write.  A write without its claim, or a reused seq, breaks the table's replacement rule: never on a live cache");
   m.def("reply_cache_clear", &launch_reply_cache_clear, py::arg("table"), py::arg("table_log2"), py::arg("stream"),
         "every entry: zero, claim all ones, epoch 0");
+
+  // ---- reply gather (gather.hip, gather.hpp): a Send's final replies reduced per call group
+  m.def("reply_gather_tile", &reply_gather_tile, "messages per tile of reply_gather");
+  m.def("reply_gather_limits", []() {
+    py::dict d;
+    d["lds_groups"] = kGatherLdsGroups;
+    d["max_groups"] = kGatherMaxGroups;
+    d["acc_words"] = kGatherAccWords;
+    d["blocks_lds"] = kGatherBlocksLds;
+    d["blocks_hbm"] = kGatherBlocksHbm;
+    d["no_row"] = kGatherNoRow;
+    d["ops"] = py::make_tuple("sum", "min", "max", "first_ne");
+    return d;
+  }, "the constants of gather.hpp: groups a block keeps in LDS, the largest G, u64 words per group's accumulator");
+  m.def("reply_gather", &launch_reply_gather, py::arg("value_in"), py::arg("status_in"), py::arg("group"), py::arg("M"),
+        py::arg("G"), py::arg("op"), py::arg("sentinel"), py::arg("acc"), py::arg("value"), py::arg("status"),
+        py::arg("n_ok"), py::arg("count"), py::arg("bad_row"), py::arg("oob"), py::arg("stream"),
+        "the M replies folded into G groups (op: index into reply_gather_limits()['ops']): the gather kernel, then the "
+        "finish kernel that writes the outputs and re-arms acc ((G + 1) * acc_words u64 holding the identities)");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

@@ -130,6 +130,15 @@ class FanOut:
             return self.answer, self.status
         return gather_ref(val, st, self.first, self.n, self.targets)
 
+    def as_gather(self):
+        """The same gather as an ``ops.gather.Gather`` for ``Send(batch, gather=...)``:
+        group = the target's index, ``first_ne`` against ``targets``.  Its ``value`` /
+        ``status`` equal ``gather``'s answer / status."""
+        from ..ops.gather import Gather
+
+        tid = torch.repeat_interleave(torch.arange(self.T, device=self.device), self.n)
+        return Gather(tid.to(torch.int32), max(1, self.T), "first_ne", self.targets if self.T else 0)
+
 
 def gather_ref(val, st, first, n, targets):
     """Host reference of the device gather (same decision per target)."""

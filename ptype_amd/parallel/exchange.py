@@ -427,16 +427,22 @@ class ActorExchange:
         return dist.all_to_all_single(out, inp, group=self.group, async_op=True)
 
     def send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None,
-             ledger=None):
+             ledger=None, gather=None):
         """Deliver every message of ``req`` (a SoA ``MsgBatch``) to its actor and return
         ``(value int64[M], status int32[M])`` in message order.  Collective:
         every rank of the group must call it (with its own, possibly empty, batch)
         the same number of times.  ``ledger``: an ``ops.ledger.Ledger`` that accounts
         this Send's replies -- one more kernel on the Send's own stream (no stream
-        fork, no host read; capturable)."""
+        fork, no host read; capturable).  ``gather``: an ``ops.gather.Gather`` that folds
+        this Send's replies into its groups -- two more kernels on the same stream,
+        capturable alike."""
+        if gather is not None:
+            gather.check_batch(req.M)
         val, st = self._send(req, out_val, out_status)
         if ledger is not None:
             ledger.account(req, val, st)
+        if gather is not None:
+            gather.reduce(val, st)
         return val, st
 
     def _send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None):
@@ -535,7 +541,7 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def capture(self, req: B.MsgBatch, out_val: torch.Tensor, out_status: torch.Tensor, prologue=None,
-                allow_collectives: bool = False, repeat: int = 1, ledger=None) -> "SendGraph":
+                allow_collectives: bool = False, repeat: int = 1, ledger=None, gather=None) -> "SendGraph":
         """Capture ``send(req)`` (plus an optional ``prologue()``, e.g. a kernel
         that refills ``req``) into a hipGraph for fixed-shape steady-state epochs:
         one graph launch replaces the ~6 kernel launches + host logic per chunk,
@@ -544,10 +550,11 @@ class ActorExchange:
         small enough that the graph launch itself shows; ``prologue(j)`` then gets
         the step's index j within the replay.  Single rank by default;
         RCCL collectives are capturable but opt-in (``allow_collectives``).
-        ``ledger``: every captured step is accounted (see ``SendGraph``)."""
+        ``ledger``: every captured step is accounted (see ``SendGraph``); ``gather``:
+        every captured step is gathered."""
         if (self.world > 1 or self.force_collectives) and not allow_collectives:
             raise RuntimeError("capture: collectives in a graph are opt-in (allow_collectives=True)")
-        return SendGraph(self, req, out_val, out_status, prologue, repeat, ledger)
+        return SendGraph(self, req, out_val, out_status, prologue, repeat, ledger, gather)
 
     # ------------------------------------------------------------------
     def pump(self, outbox, initial: B.MsgBatch | None = None, max_epochs: int = 1 << 20, check_every: int = 8):
@@ -774,7 +781,7 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def send_all(self, req: B.MsgBatch, max_epochs: int = 16, out: tuple | None = None, defer: bool = False,
-                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None, ledger=None):
+                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None, ledger=None, gather=None):
         """`send` + re-send of overflowed messages until every one is delivered.
         Reads the overflow count once per epoch (a host round trip); with adaptive
         slot capacity (native engine, wire v3) skewed traffic fits in the first
@@ -811,12 +818,21 @@ class ActorExchange:
         a message that was re-sent or retried is counted once, with the status it
         ended with.  The batch is accounted under ``logical`` actor ids when given.
         A Send with a ledger does not defer (``defer`` is treated as False, as with
-        retries): it pays the host read per re-send round that deferral avoids."""
-        if ledger is not None:
+        retries): it pays the host read per re-send round that deferral avoids.
+
+        ``gather``: an ``ops.gather.Gather`` that folds this Send's final replies into
+        its groups, once, at the same point as the ledger.  Like an accounted Send, a
+        gathered Send never defers its overflow re-sends."""
+        if ledger is not None or gather is not None:
+            if gather is not None:
+                gather.check_batch(req.M)
             val, st = self.send_all(req, max_epochs, out, False, retries, retry_on, reroute, logical)
-            if logical is not None:
-                req = B.MsgBatch(logical.to(torch.int32), req.a0, req.a1, req.a2, req.method)
-            ledger.account(req, val, st)
+            if ledger is not None:
+                if logical is not None:
+                    req = B.MsgBatch(logical.to(torch.int32), req.a0, req.a1, req.a2, req.method)
+                ledger.account(req, val, st)
+            if gather is not None:
+                gather.reduce(val, st)
             return val, st
         retries = int(retries)
         if retries < 0:
@@ -1072,10 +1088,11 @@ class SendGraph:
     handed to the captured ``send``, so every replayed step is accounted (the
     ledger kernel is one more node on the Send's own stream: no parallel branch).
     The two warm-up sends before the capture are accounted too: ``reset()`` the
-    ledger after building the graph."""
+    ledger after building the graph.  ``gather``: an ``ops.gather.Gather`` handed to
+    the captured ``send`` alike: its outputs hold the last step's groups after a replay."""
 
     def __init__(self, ex: ActorExchange, req: B.MsgBatch, out_val, out_status, prologue=None, repeat: int = 1,
-                 ledger=None):
+                 ledger=None, gather=None):
         if repeat < 1:
             raise ValueError("repeat >= 1")
         self.ex, self.req, self.M, self.repeat = ex, req, req.M, int(repeat)
@@ -1087,7 +1104,7 @@ class SendGraph:
                     prologue(j)  # the step's index within the replay
                 else:
                     prologue()
-            ex.send(req, out_val, out_status, ledger)
+            ex.send(req, out_val, out_status, ledger, gather)
 
         def body():
             for j in range(self.repeat):

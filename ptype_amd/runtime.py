@@ -365,8 +365,20 @@ class DeviceRuntime:
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
              retries: int | None = None, retry_on=None, account: bool | None = None,
-             coalesce: bool | None = None, cache: bool | None = None):
+             coalesce: bool | None = None, cache: bool | None = None, gather=None):
         """Batched Send (``_send``), optionally coalesced and answered from the reply cache.
+        ``gather``: an ``ops.gather.Gather`` over this batch -- the replies are folded
+        into its groups on the device (sum / min / max / first_ne per group, the first
+        error per group), once per Send, on the full batch's final replies in the
+        caller's order: after coalescing's fan-out, the cache hits, the retries and the
+        overflow re-sends.  The return value stays ``(value, status)`` per message; the
+        results are the object's output tensors, valid in stream order after the Send.
+        Like an accounted Send, a gathered Send never defers its overflow re-sends;
+        with ``resend_overflow=False`` the ``STATUS_OVERFLOW`` / ``STATUS_RANK_LOST`` rows are
+        simply non-OK rows.  It is the caller's view (each rank gathers the batch it
+        sent, no collective), reads nothing on the host and allocates nothing, so it
+        does not by itself forbid graph capture.  Without it a Send creates, launches
+        and reads nothing new.
         ``coalesce``: duplicate calls of a pure method (``records.PURE_METHODS``) in
         this batch -- equal ``(logical actor id, method, a0, a1, a2)`` -- are sent once
         and every duplicate gets the reply of the group's first message
@@ -407,8 +419,10 @@ class DeviceRuntime:
             coalesce = self.coalesce
         if cache is None:
             cache = self.cache
+        if gather is not None:
+            gather.check_batch(batch.M)
         if not coalesce and not cache:
-            return self._send(service, batch, resend_overflow, router, retries, retry_on, account)
+            return self._send(service, batch, resend_overflow, router, retries, retry_on, account, gather=gather)
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
@@ -443,6 +457,8 @@ class DeviceRuntime:
             out = inner(batch)
             if ledger is not None:
                 ledger.account(batch, out[0], out[1])
+            if gather is not None:
+                gather.reduce(out[0], out[1])
             return out
         if self._coalescer is None:
             from .ops.coalesce import Coalescer
@@ -451,6 +467,8 @@ class DeviceRuntime:
         out, _ = self._coalescer.send(batch, inner)
         if ledger is not None:
             ledger.account(batch, out[0], out[1])
+        if gather is not None:
+            gather.reduce(out[0], out[1])
         return out
 
     def cache_clear(self) -> None:
@@ -459,7 +477,8 @@ class DeviceRuntime:
             self._cache.clear()
 
     def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
-              retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False):
+              retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False,
+              gather=None):
         """Batched Send: every message to its actor anywhere in the node and the
         replies back in message order.  Collective across the process group.
         Registry changes seen since the last Send are applied first.  With an
@@ -476,7 +495,9 @@ class DeviceRuntime:
         this Send, True without a ledger raises.  An accounted Send does not defer
         its overflow re-sends.
         ``final``: the replies must be final on return (a coalesced Send fans them
-        out): the overflow re-sends are not deferred."""
+        out): the overflow re-sends are not deferred.
+        ``gather``: an ``ops.gather.Gather`` that folds the final replies into its groups
+        (``send``); a gathered Send does not defer its overflow re-sends either."""
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
@@ -496,11 +517,14 @@ class DeviceRuntime:
         self.sync()
         if self.membership is None:
             ex = self.exchange
-            if ledger is not None:  # accounted on its final replies: never deferred
+            if ledger is not None or gather is not None:  # on its final replies: never deferred
                 if resend_overflow:
-                    return ex.send_all(batch, logical=logical, ledger=ledger, **rkw)
+                    return ex.send_all(batch, logical=logical, ledger=ledger, gather=gather, **rkw)
                 out = ex.send(batch)
-                ledger.account(self._logical_batch(batch, logical), out[0], out[1])
+                if ledger is not None:
+                    ledger.account(self._logical_batch(batch, logical), out[0], out[1])
+                if gather is not None:
+                    gather.reduce(out[0], out[1])
                 return out
             # more than one rank: no host wait on this Send (its overflow, if any, is
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
@@ -564,6 +588,8 @@ class DeviceRuntime:
             if todo is None:
                 if ledger is not None:
                     ledger.account(self._logical_batch(batch, logical), out[0], out[1])
+                if gather is not None:
+                    gather.reduce(out[0], out[1])
                 return out
             val = torch.zeros(batch.M, dtype=out[0].dtype, device=out[0].device)
             st = torch.full((batch.M,), STATUS_RANK_LOST, dtype=out[1].dtype, device=out[1].device)
@@ -571,6 +597,8 @@ class DeviceRuntime:
             st[todo] = out[1]
             if ledger is not None:  # the whole batch, the STATUS_RANK_LOST rows included
                 ledger.account(self._logical_batch(batch, logical), val, st)
+            if gather is not None:
+                gather.reduce(val, st)
             return (val, st) + tuple(out[2:])
         raise AssertionError("unreachable")
 
