@@ -202,7 +202,7 @@ class Client:
         return self._c.go(serviceMethod, args, done)
 
     def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None,
-             cache: bool | None = None, gather=None, **kw):
+             cache: bool | None = None, gather=None, breaker: bool | None = None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -266,7 +266,26 @@ class Client:
         order after the Send and overwritten by the next Send that carries it.  It
         runs once, on the full batch's final replies (after coalescing, the cache,
         retries and overflow re-sends), costs two kernel launches and no host read,
-        and like an accounted Send never defers its overflow re-sends."""
+        and like an accounted Send never defers its overflow re-sends.
+
+        ``breaker``: the circuit breaker a Go service puts around a flaky dependency
+        (``sony/gobreaker``), per actor -- an actor whose messages failed
+        ``gpu.breaker_threshold`` times in a row (``STATUS_FAILED``, ``STATUS_NO_ACTOR`` or
+        ``STATUS_NOT_DELIVERED`` after the retries, no ``STATUS_OK`` in between) is not sent
+        to for the next ``gpu.breaker_cooldown`` guarded Sends: its messages come back
+        ``(0, STATUS_BREAKER_OPEN)`` at once.  Then one probe message per Send -- the lowest
+        of the batch that addresses it -- decides: OK closes the actor, a failure opens
+        it again (ops/breaker.py).  It wraps the retried call: the order is coalesce,
+        cache, breaker, retries.  A batch that trips nothing returns exactly what the
+        plain Send returns.  ``None`` follows ``gpu.breaker``, ``False`` skips this Send;
+        ``gpu.breaker_actors`` sizes the dense state table (8 B per actor id, default
+        every actor of the service; ids past it are never guarded).  It costs one pass
+        over the statuses and one host read per Send (a second one while any actor is
+        open), is refused under graph capture and never defers;
+        ``Stats()["runtime"]["breaker"]`` counts messages, rejected and sent ones, open
+        actors, trips and closes.  Every actor closes when the registry (or this
+        client's replica set) changed, and guarded Sends must all be issued on one
+        stream."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
@@ -277,6 +296,8 @@ class Client:
             kw.update(cache=bool(cache))
         if gather is not None:
             kw.update(gather=gather)
+        if breaker is not None:
+            kw.update(breaker=bool(breaker))
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

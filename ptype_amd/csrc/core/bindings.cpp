@@ -334,6 +334,10 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("coalesce", &GpuConfig::coalesce)
       .def_readwrite("cache", &GpuConfig::cache)
       .def_readwrite("cache_entries", &GpuConfig::cache_entries)
+      .def_readwrite("breaker", &GpuConfig::breaker)
+      .def_readwrite("breaker_threshold", &GpuConfig::breaker_threshold)
+      .def_readwrite("breaker_cooldown", &GpuConfig::breaker_cooldown)
+      .def_readwrite("breaker_actors", &GpuConfig::breaker_actors)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

@@ -137,6 +137,22 @@ void decode_ptype(const YNode& root, Config& c) {
           if (n <= 0) fail(Errc::kConfig, "gpu.cache_entries must be positive");
           c.gpu.cache_entries = (uint64_t)n;
         }
+        else if (g.first == "breaker") c.gpu.breaker = want_bool(G, g.first, g.second);
+        else if (g.first == "breaker_threshold") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 1 || n > 0xffffffffll) fail(Errc::kConfig, "gpu.breaker_threshold must be in [1, 2^32)");
+          c.gpu.breaker_threshold = (uint32_t)n;
+        }
+        else if (g.first == "breaker_cooldown") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 1 || n > 0x7ffffffell) fail(Errc::kConfig, "gpu.breaker_cooldown must be in [1, 2^31 - 2]");
+          c.gpu.breaker_cooldown = (uint32_t)n;
+        }
+        else if (g.first == "breaker_actors") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 0 || n > (1ll << 28)) fail(Errc::kConfig, "gpu.breaker_actors must be in [0, 2^28]");
+          c.gpu.breaker_actors = (uint64_t)n;
+        }
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

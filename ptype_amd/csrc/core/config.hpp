@@ -66,6 +66,10 @@ struct GpuConfig {
   bool coalesce = false;      // Send coalesces duplicate pure calls by default (ops/coalesce.py)
   bool cache = false;         // Send answers pure calls from the HBM reply cache by default (ops/reply_cache.py)
   uint64_t cache_entries = 1 << 20;  // reply cache entries (64 B each; rounded up to a power of two, [16, 1 << 26])
+  bool breaker = false;       // Send is guarded by the per-actor circuit breaker by default (ops/breaker.py)
+  uint32_t breaker_threshold = 5;  // consecutive failed messages that open an actor (>= 1)
+  uint32_t breaker_cooldown = 8;   // guarded Sends an open actor is not sent to (1 .. 2^31 - 2)
+  uint64_t breaker_actors = 0;     // breaker state words (8 B each; 0: every actor of the service)
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

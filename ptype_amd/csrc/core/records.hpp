@@ -79,6 +79,7 @@ enum ReplyStatus : int32_t {
   kStatusOverflow = 4,      // epoch bucket full; message deferred to the next epoch
   kStatusNotDelivered = 5,  // reply slot never written
   kStatusRankLost = 6,      // the actor's rank died with the message in flight (re-homed since: re-send)
+  kStatusBreakerOpen = 7,   // not sent: the actor's circuit breaker is open (csrc/hip/breaker.hpp)
 };
 
 struct alignas(16) MsgRecord {

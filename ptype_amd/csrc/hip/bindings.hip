@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "engine.hpp"
 #include "exchange_sorted.hpp"
+#include "breaker.hpp"
 #include "ipc_comm.hpp"
 #include "gather.hpp"
 #include "ledger.hpp"
@@ -127,6 +128,12 @@ void launch_reply_cache_insert(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintpt
 void launch_reply_cache_insert_phase(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t,
                                      uintptr_t, uintptr_t, int, uint32_t, uint32_t, int, uintptr_t);
 void launch_reply_cache_clear(uintptr_t, int, uintptr_t);
+int64_t breaker_tile();
+void launch_breaker_admit(uintptr_t, int64_t, uintptr_t, uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uintptr_t,
+                          uintptr_t);
+void launch_breaker_observe(uintptr_t, uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t,
+                            uint32_t, uint32_t, uint32_t, uintptr_t);
+void launch_breaker_clear(uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
 int64_t reply_gather_tile();
 void launch_reply_gather(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int, uintptr_t, uintptr_t, uintptr_t,
                          uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
@@ -435,6 +442,31 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("n_ok"), py::arg("count"), py::arg("bad_row"), py::arg("oob"), py::arg("stream"),
         "the M replies folded into G groups (op: index into reply_gather_limits()['ops']): the gather kernel, then the "
         "finish kernel that writes the outputs and re-arms acc ((G + 1) * acc_words u64 holding the identities)");
+
+  // ---- circuit breaker (breaker.hip, breaker.hpp): failing actors not sent to, per actor, across Sends
+  m.def("breaker_tile", &breaker_tile, "messages per tile of the breaker's streaming kernels");
+  m.def("breaker_limits", []() {
+    py::dict d;
+    d["pending"] = kBreakerPending;
+    d["status"] = (int)kStatusBreakerOpen;
+    d["max_tick"] = kBreakerMaxTick;
+    d["max_actors"] = kBreakerMaxActors;
+    d["ctr_words"] = kBreakerCtrWords;
+    d["counters"] = py::make_tuple("n_open", "n_dirty", "trips", "closes", "oob", "n_touched");
+    return d;
+  }, "the constants of breaker.hpp: the marker status, STATUS_BREAKER_OPEN, the last tick, the largest table, the "
+     "counter block's u64 words and the names of its first words");
+  m.def("breaker_admit", &launch_breaker_admit, py::arg("actor"), py::arg("M"), py::arg("word"), py::arg("probe"),
+        py::arg("n"), py::arg("now"), py::arg("ctr"), py::arg("val"), py::arg("st"), py::arg("stream"),
+        "the probe launch (rows of half-open actors claim probe[a]) and the admit launch: st[i] = the marker for a row "
+        "that travels, STATUS_BREAKER_OPEN for a rejected one, val[i] = 0; ids >= n pass and are counted");
+  m.def("breaker_observe", &launch_breaker_observe, py::arg("actor"), py::arg("st"), py::arg("K"), py::arg("trip_mask"),
+        py::arg("word"), py::arg("obs"), py::arg("touched"), py::arg("ctr"), py::arg("n"), py::arg("now"),
+        py::arg("threshold"), py::arg("cooldown"), py::arg("stream"),
+        "the final statuses of the K rows that travelled folded into the state words: the bad-row launch, the ok "
+        "launch, the step launch (which zeroes obs and re-arms the touched count)");
+  m.def("breaker_clear", &launch_breaker_clear, py::arg("word"), py::arg("obs"), py::arg("probe"), py::arg("ctr"),
+        py::arg("n"), py::arg("stream"), "every word and obs 0, every probe all ones, n_open / n_dirty / n_touched 0");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

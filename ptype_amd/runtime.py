@@ -72,7 +72,9 @@ class DeviceRuntime:
                  delay_us: int = 0, max_batch: int = 1 << 20, chunks: int = 0, random_state: bool = False,
                  group=None, shm: bool = True, service: str = "", mailbox_shards: int = 256,
                  mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0,
-                 ledger: bool = False, coalesce: bool = False, cache: bool = False, cache_entries: int = 1 << 20):
+                 ledger: bool = False, coalesce: bool = False, cache: bool = False, cache_entries: int = 1 << 20,
+                 breaker: bool = False, breaker_threshold: int = 5, breaker_cooldown: int = 8,
+                 breaker_actors: int = 0, breaker_trip_on=None):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -149,6 +151,19 @@ class DeviceRuntime:
         self._cache = None
         self._registry_changes = 0
         self._cache_seen = None
+        # Circuit breaker (ops/breaker.py): the default of send(breaker=None), its settings, the
+        # state table with its host counters (created by the first guarded Send; breaker_actors 0:
+        # one word per actor of the service) and what the last guarded Send saw of the registry
+        from .ops.breaker import BreakerRef
+
+        self.breaker = bool(breaker)
+        self.breaker_threshold, self.breaker_cooldown = int(breaker_threshold), int(breaker_cooldown)
+        self.breaker_actors, self.breaker_trip_on = int(breaker_actors), breaker_trip_on
+        if self.breaker_actors < 0:
+            raise ValueError("breaker_actors must be >= 0 (0: every actor of the service)")
+        BreakerRef("cpu", 1, self.breaker_threshold, self.breaker_cooldown, breaker_trip_on)  # (validates the settings)
+        self._breaker = None
+        self._breaker_seen = None
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -213,7 +228,9 @@ class DeviceRuntime:
                  max_batch=g.max_batch, service=cfg.service_name, mailbox_shards=g.mailbox_shards,
                  mailbox_slots=g.mailbox_slots, delivery=g.delivery, comm=g.comm,
                  comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger, coalesce=g.coalesce,
-                 cache=g.cache, cache_entries=g.cache_entries)
+                 cache=g.cache, cache_entries=g.cache_entries, breaker=g.breaker,
+                 breaker_threshold=g.breaker_threshold, breaker_cooldown=g.breaker_cooldown,
+                 breaker_actors=g.breaker_actors)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -365,8 +382,9 @@ class DeviceRuntime:
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
              retries: int | None = None, retry_on=None, account: bool | None = None,
-             coalesce: bool | None = None, cache: bool | None = None, gather=None):
-        """Batched Send (``_send``), optionally coalesced and answered from the reply cache.
+             coalesce: bool | None = None, cache: bool | None = None, gather=None, breaker: bool | None = None):
+        """Batched Send (``_send``), optionally coalesced, answered from the reply cache and
+        guarded by the circuit breaker.
         ``gather``: an ``ops.gather.Gather`` over this batch -- the replies are folded
         into its groups on the device (sum / min / max / first_ne per group, the first
         error per group), once per Send, on the full batch's final replies in the
@@ -414,26 +432,74 @@ class DeviceRuntime:
         the ledger accounts the full batch once, hits included.  The table is state
         that outlives the Send and stream order is its only protection: every cached
         Send of a runtime must be issued on the same stream (or on streams the caller
-        orders after one another)."""
+        orders after one another).
+        ``breaker``: a circuit breaker per logical actor id (ops/breaker.py: gobreaker, Akka's
+        ``CircuitBreaker``).  An actor whose messages failed ``breaker_threshold`` times in a
+        row -- a final status in ``breaker_trip_on``, by default ``STATUS_FAILED``,
+        ``STATUS_NO_ACTOR`` or ``STATUS_NOT_DELIVERED``, with no ``STATUS_OK`` in between -- is
+        open for the next ``breaker_cooldown`` guarded Sends: its messages are answered
+        ``(0, STATUS_BREAKER_OPEN)`` and not sent.  After that the lowest message of a batch
+        that addresses it travels as the probe (every other one is still rejected): OK closes
+        the actor, a failure opens it for another cooldown.  None follows the runtime's
+        setting (``DeviceRuntime(breaker=...)``, ``gpu.breaker``), False skips this Send.  The
+        order is fixed: coalesce, cache, breaker, then the Send below -- a breaker wraps the
+        retried call, so retries, the router, the elastic loop and the overflow re-sends see
+        only the admitted rows, as one sub-batch in message order (an ordered method keeps
+        its per-actor FIFO), and the final status after the retries is what the breaker
+        observes.  A coalesced follower inherits its leader's ``STATUS_BREAKER_OPEN``; the
+        cache never stores it (and a cached hit is never sent, so it passes an open breaker);
+        the ledger counts it under "other"; a gather sees a non-OK row.  The inner Send runs
+        exactly once per guarded Send at world > 1 (a rank whose batch was all rejected joins
+        with an empty batch); at world 1 with nothing admitted it is skipped.  Time is
+        counted in guarded Sends.  Every actor closes (``breaker_reset()`` does it by hand)
+        when anything that decides whether an actor exists has changed since the last
+        guarded Send, or when the same router's record set has; another router object alone
+        does not reset.  A guarded Send reads the number of open actors on the host (and K
+        when there are any), so it is refused under graph capture and never defers; with
+        nothing open the batch is sent untouched and only the observation kernels follow.
+        Like the cache's, its tables outlive the Send: all guarded Sends of a runtime go on
+        one stream."""
         if coalesce is None:
             coalesce = self.coalesce
         if cache is None:
             cache = self.cache
+        if breaker is None:
+            breaker = self.breaker
         if gather is not None:
             gather.check_batch(batch.M)
-        if not coalesce and not cache:
+        if not coalesce and not cache and not breaker:
             return self._send(service, batch, resend_overflow, router, retries, retry_on, account, gather=gather)
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
         if (self._exchange is not None and self._exchange._capturing) or (
                 self.on_gpu and torch.cuda.is_current_stream_capturing()):
-            if not coalesce:
+            if coalesce:
+                raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
+            if cache:
                 raise ValueError("send(cache=True) inside a captured Send: selecting the misses needs a host read")
-            raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
+            raise ValueError("send(breaker=True) inside a captured Send: the count of open actors is read on the host")
         ledger = self.ledger if account is None or account else None
         # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
         inner = (lambda sub: self._send(service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+        if breaker:
+            if self._breaker is None:
+                from .ops.breaker import Breaker
+
+                self._breaker = Breaker(self.device, self.breaker_actors or self.total_actors, self.breaker_threshold,
+                                        self.breaker_cooldown, self.breaker_trip_on)
+            self.sync()
+            if router is not None:
+                router.refresh()
+            else:
+                self._check_service(service)  # (an all-rejected Send never reaches _send's check)
+            seen = (self._registry_changes, router, None if router is None else router.changes)
+            last = self._breaker_seen
+            if last is not None and (seen[0] != last[0] or (seen[1] is last[1] and seen[2] != last[2])):
+                self._breaker.reset()
+            self._breaker_seen = seen
+            unguarded = inner
+            inner = (lambda sub: self._breaker.send(sub, unguarded, collective=self.world > 1))
         if cache:
             if self._cache is None:
                 from .ops.reply_cache import ReplyCache
@@ -475,6 +541,11 @@ class DeviceRuntime:
         """Drop every entry of the reply cache (O(1): the cache's epoch moves on)."""
         if self._cache is not None:
             self._cache.clear()
+
+    def breaker_reset(self) -> None:
+        """Close every actor's circuit breaker (the breaker's tick goes on)."""
+        if self._breaker is not None:
+            self._breaker.reset()
 
     def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
               retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False,
@@ -930,6 +1001,13 @@ class DeviceRuntime:
                            else {"sends": 0, "messages": 0, "executed": 0})
         out["cache"] = (dict(self._cache.counters, entries=self._cache.entries) if self._cache is not None
                         else {"sends": 0, "messages": 0, "hits": 0, "sent": 0, "clears": 0, "entries": 0})
+        if self._breaker is not None:
+            b, r = self._breaker, self._breaker.read()  # (one host read of the device counters)
+            out["breaker"] = dict(b.counters, open=r["open"], trips=r["trips"], closes=r["closes"], oob=r["oob"],
+                                  actors=b.n, threshold=b.threshold, cooldown=b.cooldown)
+        else:
+            out["breaker"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "open": 0, "trips": 0, "closes": 0,
+                              "oob": 0, "actors": 0, "threshold": 0, "cooldown": 0}
         return out
 
     def close(self) -> None:
