@@ -202,7 +202,8 @@ class Client:
         return self._c.go(serviceMethod, args, done)
 
     def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None,
-             cache: bool | None = None, gather=None, breaker: bool | None = None, **kw):
+             cache: bool | None = None, gather=None, breaker: bool | None = None, limit: bool | None = None,
+             **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -285,7 +286,23 @@ class Client:
         ``Stats()["runtime"]["breaker"]`` counts messages, rejected and sent ones, open
         actors, trips and closes.  Every actor closes when the registry (or this
         client's replica set) changed, and guarded Sends must all be issued on one
-        stream."""
+        stream.
+
+        ``limit``: the rate limiter a Go service puts in front of a dependency
+        (``golang.org/x/time/rate``), per actor -- a token bucket that gains ``gpu.limit_rate``
+        tokens per limited Send and holds at most ``gpu.limit_burst``.  Every message that
+        travels costs one token; of an actor whose messages in this batch exceed its tokens
+        the first ones in message order travel and the others come back
+        ``(0, STATUS_THROTTLED)`` at once (ops/limit.py).  It is the innermost wrapper: the
+        order is coalesce, cache, breaker, limit, retries, so followers, cached hits and
+        breaker-rejected messages cost nothing and a retried message costs one token.
+        ``None`` follows ``gpu.limit``, ``False`` skips this Send; ``gpu.limit_actors`` sizes
+        the dense bucket table (8 B per actor id, default every actor of the service; ids
+        past it are never limited).  It costs one pass over the actor ids and one host read
+        per Send (more passes and a second read only while some actor is over its quota), is
+        refused under graph capture and never defers; ``Stats()["runtime"]["limit"]`` counts
+        messages, throttled and sent ones.  Registry changes reset nothing, and limited
+        Sends must all be issued on one stream."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
@@ -298,6 +315,8 @@ class Client:
             kw.update(gather=gather)
         if breaker is not None:
             kw.update(breaker=bool(breaker))
+        if limit is not None:
+            kw.update(limit=bool(limit))
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
     def Flush(self) -> None:

@@ -338,6 +338,10 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("breaker_threshold", &GpuConfig::breaker_threshold)
       .def_readwrite("breaker_cooldown", &GpuConfig::breaker_cooldown)
       .def_readwrite("breaker_actors", &GpuConfig::breaker_actors)
+      .def_readwrite("limit", &GpuConfig::limit)
+      .def_readwrite("limit_rate", &GpuConfig::limit_rate)
+      .def_readwrite("limit_burst", &GpuConfig::limit_burst)
+      .def_readwrite("limit_actors", &GpuConfig::limit_actors)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

@@ -153,6 +153,22 @@ void decode_ptype(const YNode& root, Config& c) {
           if (n < 0 || n > (1ll << 28)) fail(Errc::kConfig, "gpu.breaker_actors must be in [0, 2^28]");
           c.gpu.breaker_actors = (uint64_t)n;
         }
+        else if (g.first == "limit") c.gpu.limit = want_bool(G, g.first, g.second);
+        else if (g.first == "limit_rate") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 1 || n > 0xffffffffll) fail(Errc::kConfig, "gpu.limit_rate must be in [1, 2^32)");
+          c.gpu.limit_rate = (uint32_t)n;
+        }
+        else if (g.first == "limit_burst") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 1 || n > 0xffffffffll) fail(Errc::kConfig, "gpu.limit_burst must be in [1, 2^32)");
+          c.gpu.limit_burst = (uint32_t)n;
+        }
+        else if (g.first == "limit_actors") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 0 || n > (1ll << 28)) fail(Errc::kConfig, "gpu.limit_actors must be in [0, 2^28]");
+          c.gpu.limit_actors = (uint64_t)n;
+        }
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

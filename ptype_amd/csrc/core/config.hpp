@@ -70,6 +70,10 @@ struct GpuConfig {
   uint32_t breaker_threshold = 5;  // consecutive failed messages that open an actor (>= 1)
   uint32_t breaker_cooldown = 8;   // guarded Sends an open actor is not sent to (1 .. 2^31 - 2)
   uint64_t breaker_actors = 0;     // breaker state words (8 B each; 0: every actor of the service)
+  bool limit = false;          // Send is rate-limited per actor by default (ops/limit.py)
+  uint32_t limit_rate = 1;    // tokens an actor gains per limited Send (>= 1)
+  uint32_t limit_burst = 1;   // bucket size: the most messages of one actor a Send admits (>= 1)
+  uint64_t limit_actors = 0;  // limiter state words (8 B each; 0: every actor of the service)
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

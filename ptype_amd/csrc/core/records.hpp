@@ -80,6 +80,7 @@ enum ReplyStatus : int32_t {
   kStatusNotDelivered = 5,  // reply slot never written
   kStatusRankLost = 6,      // the actor's rank died with the message in flight (re-homed since: re-send)
   kStatusBreakerOpen = 7,   // not sent: the actor's circuit breaker is open (csrc/hip/breaker.hpp)
+  kStatusThrottled = 8,     // not sent: the actor's token bucket is empty (csrc/hip/limit.hpp)
 };
 
 struct alignas(16) MsgRecord {

@@ -16,6 +16,7 @@
 #include "ipc_comm.hpp"
 #include "gather.hpp"
 #include "ledger.hpp"
+#include "limit.hpp"
 #include "mailbox.hpp"
 #include "reply_cache.hpp"
 #include "server.hpp"
@@ -134,6 +135,12 @@ void launch_breaker_admit(uintptr_t, int64_t, uintptr_t, uintptr_t, int64_t, uin
 void launch_breaker_observe(uintptr_t, uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t,
                             uint32_t, uint32_t, uint32_t, uintptr_t);
 void launch_breaker_clear(uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
+int64_t limit_tile();
+void launch_limit_demand(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                         uintptr_t, int64_t, uint32_t, uint32_t, uint32_t, uintptr_t);
+void launch_limit_cut(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t,
+                      uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t);
+void launch_limit_clear(uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
 int64_t reply_gather_tile();
 void launch_reply_gather(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int, uintptr_t, uintptr_t, uintptr_t,
                          uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
@@ -467,6 +474,39 @@ PYBIND11_MODULE(_hip, m) {
         "launch, the step launch (which zeroes obs and re-arms the touched count)");
   m.def("breaker_clear", &launch_breaker_clear, py::arg("word"), py::arg("obs"), py::arg("probe"), py::arg("ctr"),
         py::arg("n"), py::arg("stream"), "every word and obs 0, every probe all ones, n_open / n_dirty / n_touched 0");
+
+  // ---- rate limiter (limit.hip, limit.hpp): a token bucket per actor, the over-quota rows cut in message order
+  m.def("limit_tile", &limit_tile, "messages per tile of the limiter's streaming kernels");
+  m.def("limit_limits", []() {
+    py::dict d;
+    d["pending"] = kLimitPending;
+    d["status"] = (int)kStatusThrottled;
+    d["max_tick"] = kLimitMaxTick;
+    d["max_actors"] = kLimitMaxActors;
+    d["max_hot"] = kLimitMaxHot;
+    d["digit"] = kLimitDigit;
+    d["hot"] = kLimitHot;
+    d["ctr_words"] = kLimitCtrWords;
+    d["busy_cap"] = kLimitBusyCap;
+    d["counters"] = py::make_tuple("throttled", "oob", "over", "n_touched");
+    return d;
+  }, "the constants of limit.hpp: the marker status, STATUS_THROTTLED, the last tick, the largest table, the most hot "
+     "slots of one Send, the radix select's digit width, the hot flag of demand[], the counter block's u64 words and "
+     "the names of its first words");
+  m.def("limit_levels", [](int64_t M) { return limit_levels(M); }, py::arg("M"),
+        "levels of the radix select over the row indices of M messages");
+  m.def("limit_demand", &launch_limit_demand, py::arg("actor"), py::arg("M"), py::arg("word"), py::arg("demand"),
+        py::arg("touched"), py::arg("hot_actor"), py::arg("rem"), py::arg("prefix"), py::arg("busy"), py::arg("ctr"),
+        py::arg("n"), py::arg("now"), py::arg("rate"), py::arg("burst"), py::arg("stream"),
+        "the demand launch (rows per actor, ids >= n counted) and the step launch: the refill, the admitted count and "
+        "the new word of every addressed actor; the actors over their quota get a hot slot, ctr's `over` counts them");
+  m.def("limit_cut", &launch_limit_cut, py::arg("actor"), py::arg("M"), py::arg("demand"), py::arg("hot_actor"),
+        py::arg("rem"), py::arg("prefix"), py::arg("ctr"), py::arg("n"), py::arg("over"), py::arg("slot"),
+        py::arg("bins"), py::arg("bins_words"), py::arg("val"), py::arg("st"), py::arg("stream"),
+        "with over > 0 hot slots: the radix select of each hot actor's threshold row, st[i] = the marker for a row that "
+        "travels, STATUS_THROTTLED for a rejected one, val[i] = 0, then the re-arm of demand and `over`");
+  m.def("limit_clear", &launch_limit_clear, py::arg("word"), py::arg("demand"), py::arg("ctr"), py::arg("n"),
+        py::arg("stream"), "every word and demand 0, over / n_touched 0");
 
   // ---- wire format v3 (packed.hpp): standalone kernels for tests and tools; the
   // epoch engine drives them itself (meta all-reduce + layout) in a Send

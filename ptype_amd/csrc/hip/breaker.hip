@@ -34,37 +34,14 @@
 // near-empty launches.  obs[a] is only written by atomics (bad: add, ok: or) and zeroed by
 // the one step thread that owns a, so every count is exact whatever the arrival order.
 //
-// Tile layout as in gather.hip: 256 threads x kBrRows rows; row j of wave w, lane l covers
-// the messages  tile * kBrTile + (j * 4 + w) * 256 + l * 4 + {0, 1, 2, 3}: one dwordx4 per
-// lane.  A column that is not 16-byte aligned takes the same layout with scalar loads.
+// Tile layout, loads, run combining and the touched[] reservation: runs.hpp.
 #include "breaker.hpp"
 #include "common.hpp"
+#include "runs.hpp"
 
 namespace ptype {
 
-constexpr int kBrThreads = 256;
-constexpr int kBrWaves = kBrThreads / kWave;
-constexpr int kBrRows = 2;                             // 4-message rows per thread and tile
-constexpr int kBrTile = kBrThreads * kBrRows * 4;      // 2048 messages
-constexpr int kBrBlocks = 2048;                        // blocks of a streaming launch (they stride over the tiles)
 constexpr int kBrStepBlocks = 64;
-constexpr uint32_t kBrNoActor = 0xffffffffu;           // a row past M (never < n)
-
-__device__ __forceinline__ int64_t br_elem(int64_t tile, int j, unsigned wave, unsigned lane) {
-  return tile * kBrTile + (int64_t)(j * kBrWaves + (int)wave) * (kWave * 4) + lane * 4;
-}
-
-// Four consecutive elements at index i (a multiple of 4); elements at or past M read as `pad`.
-template <bool ALIGNED>
-__device__ __forceinline__ void br_load4(const int* __restrict__ p, int64_t i, int64_t M, int pad, int (&o)[4]) {
-  if (ALIGNED && i + 4 <= M) {
-    const int4 v = *reinterpret_cast<const int4*>(p + i);
-    o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    return;
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) o[c] = i + c < M ? p[i + c] : pad;
-}
 
 __device__ __forceinline__ bool br_half_open(uint64_t w, uint32_t now) {
   return breaker_is_open(w) && now >= breaker_until(w);
@@ -150,29 +127,13 @@ __global__ __launch_bounds__(kBrThreads) void breaker_admit_kernel(const int* __
 }
 static_assert(kBrWaves == 4, "the oob reduction reads four waves' partials");
 
-// Every lane of the wave calls this together.  The lanes with `fresh` (their atomic took
-// obs[a] from 0) reserve their places in touched[] with one atomic and write a there.
-__device__ __forceinline__ void br_append(bool fresh, uint32_t a, unsigned long long* __restrict__ ctr,
-                                          uint32_t* __restrict__ touched, uint32_t n) {
-  const uint64_t m = __ballot(fresh);
-  if (!m) return;  // (wave-uniform)
-  const int leader = __ffsll((long long)m) - 1;
-  unsigned long long base = 0;
-  if ((int)lane_id() == leader) base = atomicAdd(&ctr[kBreakerTouched], (unsigned long long)__popcll(m));
-  base = __shfl(base, leader, kWave);
-  if (fresh) {
-    const unsigned long long pos = base + mbcnt64(m);
-    if (pos < n) touched[pos] = a;  // (an actor is appended once per Send: pos < n always)
-  }
-}
-
 // Every lane of the wave calls this together: run (g, cnt) of failed rows, g < 0 for none.
 __device__ __forceinline__ void br_emit_bad(int g, uint32_t cnt, unsigned long long* __restrict__ obs,
                                             unsigned long long* __restrict__ ctr, uint32_t* __restrict__ touched,
                                             uint32_t n) {
   bool fresh = false;
   if (g >= 0) fresh = atomicAdd(&obs[g], (unsigned long long)cnt) == 0ull;
-  br_append(fresh, (uint32_t)g, ctr, touched, n);
+  br_append(fresh, (uint32_t)g, ctr + kBreakerTouched, touched, n);
 }
 
 template <bool ALIGNED>
@@ -202,47 +163,7 @@ __global__ __launch_bounds__(kBrThreads) void breaker_observe_bad_kernel(const i
       }
       if (!__ballot(any)) continue;  // (wave-uniform) the healthy Send: nothing but the stream
 
-      // the thread's four rows: head run, tail run, runs in between added at once
-      int cur_g = g[0], head_g = g[0];
-      uint32_t cur_n = g[0] >= 0, head_n = 0;
-      bool single = true;
-#pragma unroll
-      for (int c = 1; c < 4; ++c) {
-        int flush_g = -1;
-        uint32_t flush_n = 0;
-        if (g[c] == cur_g) {
-          cur_n += g[c] >= 0;
-        } else {
-          if (single)
-            head_g = cur_g, head_n = cur_n, single = false;
-          else
-            flush_g = cur_g, flush_n = cur_n;
-          cur_g = g[c], cur_n = g[c] >= 0;
-        }
-        if (c >= 2) br_emit_bad(flush_g, flush_n, obs, ctr, touched, n);
-      }
-      const int tail_g = cur_g;
-      if (single) head_g = tail_g;
-
-      // across the wave: the items are the tails; an item starts a run unless the lane is
-      // one run that continues the previous lane's tail
-      const int prev_tail_g = __shfl_up(tail_g, 1, kWave);
-      const int next_head_g = __shfl_down(head_g, 1, kWave);
-      const bool starts = lane == 0 || !single || tail_g != prev_tail_g;
-      const uint64_t heads = __ballot(starts);
-      if (heads != ~0ull) {  // (wave-uniform)
-        const unsigned first = 63u - (unsigned)__clzll((long long)(heads & ((2ull << lane) - 1ull)));
-#pragma unroll
-        for (unsigned o = 1; o < (unsigned)kWave; o <<= 1) {
-          const uint32_t up = (uint32_t)__shfl_up((int)cur_n, o, kWave);
-          if (lane >= first + o) cur_n += up;
-        }
-      }
-      const uint32_t prev_n = (uint32_t)__shfl_up((int)cur_n, 1, kWave);
-      if (!single && lane > 0 && head_g == prev_tail_g) head_n += prev_n;
-      br_emit_bad(single ? -1 : head_g, head_n, obs, ctr, touched, n);
-      const bool last = lane == (unsigned)kWave - 1 || next_head_g != tail_g;
-      br_emit_bad(last ? tail_g : -1, cur_n, obs, ctr, touched, n);
+      br_combine_runs(g, lane, [&](int run_g, uint32_t run_n) { br_emit_bad(run_g, run_n, obs, ctr, touched, n); });
     }
   }
 }
@@ -284,7 +205,7 @@ __global__ __launch_bounds__(kBrThreads) void breaker_observe_ok_kernel(const in
           if ((word[a[c]] | o) != 0ull && !(o & kBreakerObsOk))
             fresh = atomicOr(&obs[a[c]], (unsigned long long)kBreakerObsOk) == 0ull;
         }
-        br_append(fresh, a[c], ctr, touched, n);
+        br_append(fresh, a[c], ctr + kBreakerTouched, touched, n);
       }
     }
   }

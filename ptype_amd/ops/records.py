@@ -42,6 +42,7 @@ STATUS_OVERFLOW = 4
 STATUS_NOT_DELIVERED = 5
 STATUS_RANK_LOST = 6  # the actor's rank died with the message in flight (re-homed since: re-send)
 STATUS_BREAKER_OPEN = 7  # not sent: the actor's circuit breaker is open (ops/breaker.py)
+STATUS_THROTTLED = 8  # not sent: the actor's token bucket is empty (ops/limit.py)
 
 # names for people (Stats(), the Send ledger): the net/rpc service methods the ids stand for
 METHOD_NAMES = {
@@ -52,7 +53,7 @@ METHOD_NAMES = {
 STATUS_NAMES = {
     STATUS_OK: "ok", STATUS_NO_METHOD: "no_method", STATUS_FAILED: "failed", STATUS_NO_ACTOR: "no_actor",
     STATUS_OVERFLOW: "overflow", STATUS_NOT_DELIVERED: "not_delivered", STATUS_RANK_LOST: "rank_lost",
-    STATUS_BREAKER_OPEN: "breaker_open",
+    STATUS_BREAKER_OPEN: "breaker_open", STATUS_THROTTLED: "throttled",
 }
 
 MSG_WORDS = 4    # int64 words per 32-B message record

@@ -74,7 +74,8 @@ class DeviceRuntime:
                  mailbox_slots: int = 0, delivery: str = "auto", comm: str = "rccl", comm_timeout_s: float = 30.0,
                  ledger: bool = False, coalesce: bool = False, cache: bool = False, cache_entries: int = 1 << 20,
                  breaker: bool = False, breaker_threshold: int = 5, breaker_cooldown: int = 8,
-                 breaker_actors: int = 0, breaker_trip_on=None):
+                 breaker_actors: int = 0, breaker_trip_on=None, limit: bool = False, limit_rate: int = 1,
+                 limit_burst: int = 1, limit_actors: int = 0):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -164,6 +165,17 @@ class DeviceRuntime:
         BreakerRef("cpu", 1, self.breaker_threshold, self.breaker_cooldown, breaker_trip_on)  # (validates the settings)
         self._breaker = None
         self._breaker_seen = None
+        # Rate limiter (ops/limit.py): the default of send(limit=None), its settings and the
+        # bucket table with its host counters (created by the first limited Send; limit_actors 0:
+        # one word per actor of the service)
+        from .ops.limit import LimiterRef
+
+        self.limit = bool(limit)
+        self.limit_rate, self.limit_burst, self.limit_actors = int(limit_rate), int(limit_burst), int(limit_actors)
+        if self.limit_actors < 0:
+            raise ValueError("limit_actors must be >= 0 (0: every actor of the service)")
+        LimiterRef("cpu", 1, self.limit_rate, self.limit_burst)  # (validates the settings)
+        self._limiter = None
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -230,7 +242,8 @@ class DeviceRuntime:
                  comm_timeout_s=g.group_timeout_s, group=native, ledger=g.ledger, coalesce=g.coalesce,
                  cache=g.cache, cache_entries=g.cache_entries, breaker=g.breaker,
                  breaker_threshold=g.breaker_threshold, breaker_cooldown=g.breaker_cooldown,
-                 breaker_actors=g.breaker_actors)
+                 breaker_actors=g.breaker_actors, limit=g.limit, limit_rate=g.limit_rate,
+                 limit_burst=g.limit_burst, limit_actors=g.limit_actors)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -382,9 +395,10 @@ class DeviceRuntime:
 
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
              retries: int | None = None, retry_on=None, account: bool | None = None,
-             coalesce: bool | None = None, cache: bool | None = None, gather=None, breaker: bool | None = None):
-        """Batched Send (``_send``), optionally coalesced, answered from the reply cache and
-        guarded by the circuit breaker.
+             coalesce: bool | None = None, cache: bool | None = None, gather=None, breaker: bool | None = None,
+             limit: bool | None = None):
+        """Batched Send (``_send``), optionally coalesced, answered from the reply cache,
+        guarded by the circuit breaker and rate-limited per actor.
         ``gather``: an ``ops.gather.Gather`` over this batch -- the replies are folded
         into its groups on the device (sum / min / max / first_ne per group, the first
         error per group), once per Send, on the full batch's final replies in the
@@ -458,16 +472,41 @@ class DeviceRuntime:
         when there are any), so it is refused under graph capture and never defers; with
         nothing open the batch is sent untouched and only the observation kernels follow.
         Like the cache's, its tables outlive the Send: all guarded Sends of a runtime go on
-        one stream."""
+        one stream.
+        ``limit``: a token bucket per logical actor id (ops/limit.py: ``golang.org/x/time/rate``,
+        Akka's ``throttle``).  An actor gains ``limit_rate`` tokens per limited Send and holds at
+        most ``limit_burst``; every message that travels costs one.  Of an actor whose rows
+        exceed its tokens the first ones in message order travel, the others are answered
+        ``(0, STATUS_THROTTLED)`` and not sent.  None follows the runtime's setting
+        (``DeviceRuntime(limit=...)``, ``gpu.limit``), False skips this Send.  The order is
+        fixed: coalesce, cache, breaker, limit, then the Send below -- the limiter is the
+        innermost wrapper, so a token is spent only by a row that actually travels: followers,
+        cache hits and breaker-rejected rows cost nothing, and a row that is retried or re-sent
+        after an overflow costs one token for all its attempts.  The admitted rows go on as one
+        sub-batch in message order (an ordered method keeps its per-actor FIFO).  A coalesced
+        follower inherits its leader's ``STATUS_THROTTLED``; the cache never stores it; the
+        breaker's ``trip_on`` cannot name it, so a throttled row counts as neither OK nor bad
+        there and a throttled probe leaves its actor half-open; the ledger counts it under
+        "other"; a gather sees a non-OK row.  The inner Send runs exactly once per limited Send
+        at world > 1 (a rank whose batch was all throttled joins with an empty batch); at
+        world 1 with nothing admitted it is skipped.  Time is counted in limited Sends.  The
+        buckets do not depend on whether an actor exists: registry or router changes reset
+        nothing, ``limit_reset()`` fills every bucket by hand.  A limited Send reads the number
+        of actors over their quota on the host (and K when there are any), so it is refused
+        under graph capture and never defers; with nothing over quota the batch is sent
+        untouched after two launches.  Its tables outlive the Send: all limited Sends of a
+        runtime go on one stream."""
         if coalesce is None:
             coalesce = self.coalesce
         if cache is None:
             cache = self.cache
         if breaker is None:
             breaker = self.breaker
+        if limit is None:
+            limit = self.limit
         if gather is not None:
             gather.check_batch(batch.M)
-        if not coalesce and not cache and not breaker:
+        if not coalesce and not cache and not breaker and not limit:
             return self._send(service, batch, resend_overflow, router, retries, retry_on, account, gather=gather)
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
@@ -478,10 +517,24 @@ class DeviceRuntime:
                 raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
             if cache:
                 raise ValueError("send(cache=True) inside a captured Send: selecting the misses needs a host read")
-            raise ValueError("send(breaker=True) inside a captured Send: the count of open actors is read on the host")
+            if breaker:
+                raise ValueError("send(breaker=True) inside a captured Send: the count of open actors is read on the "
+                                 "host")
+            raise ValueError("send(limit=True) inside a captured Send: the count of actors over their quota is read on "
+                             "the host")
         ledger = self.ledger if account is None or account else None
         # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
         inner = (lambda sub: self._send(service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+        if limit:
+            if self._limiter is None:
+                from .ops.limit import Limiter
+
+                self._limiter = Limiter(self.device, self.limit_actors or self.total_actors, self.limit_rate,
+                                        self.limit_burst)
+            if router is None:
+                self._check_service(service)  # (an all-throttled Send never reaches _send's check)
+            unlimited = inner
+            inner = (lambda sub: self._limiter.send(sub, unlimited, collective=self.world > 1))
         if breaker:
             if self._breaker is None:
                 from .ops.breaker import Breaker
@@ -546,6 +599,11 @@ class DeviceRuntime:
         """Close every actor's circuit breaker (the breaker's tick goes on)."""
         if self._breaker is not None:
             self._breaker.reset()
+
+    def limit_reset(self) -> None:
+        """Fill every actor's token bucket (the limiter's tick goes on)."""
+        if self._limiter is not None:
+            self._limiter.reset()
 
     def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
               retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False,
@@ -1008,6 +1066,13 @@ class DeviceRuntime:
         else:
             out["breaker"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "open": 0, "trips": 0, "closes": 0,
                               "oob": 0, "actors": 0, "threshold": 0, "cooldown": 0}
+        if self._limiter is not None:
+            lim, r = self._limiter, self._limiter.read()  # (one host read of the device counters)
+            out["limit"] = dict(lim.counters, throttled=r["throttled"], oob=r["oob"], actors=lim.n, rate=lim.rate,
+                                burst=lim.burst)
+        else:
+            out["limit"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "throttled": 0, "oob": 0, "actors": 0,
+                            "rate": 0, "burst": 0}
         return out
 
     def close(self) -> None:
