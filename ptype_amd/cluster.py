@@ -319,6 +319,26 @@ class Client:
             kw.update(limit=bool(limit))
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
 
+    def Ask(self, questions, scatter, op: str = "sum", sentinel=None, **kw):
+        """Scatter-gather on the device: the optimus coordinator's ``splitWork`` ..
+        ``watchReplies`` (coordinator.go:67-98) for any rule and op.  ``scatter`` -- an
+        ``ops.scatter.Scatter``: ``Scatter.ranges(step, n_actors, first_lo)`` is
+        ``splitWork``, ``Scatter.members(offsets, members)`` one call to every member of a
+        group -- expands the Q ``questions`` (a short ``MsgBatch``) into T calls with HIP
+        kernels, the calls go through ``Send`` with every keyword it takes (``retries``,
+        ``coalesce``, ``cache``, ``breaker``, ``limit``, ``account``) and the replies are folded
+        per question with ``op`` (``sum``, ``min``, ``max`` or ``first_ne`` against
+        ``sentinel``).  Returns an ``ops.scatter.Answer``: ``value``, ``status``, ``n_ok``,
+        ``count`` and ``bad_row`` per question, the expansion's ``first``, ``n`` and ``oob``,
+        and the per-call ``(val, st)``.  It costs four launches and one 16-byte host read
+        on top of the Send, so it is refused under graph capture (expand first and capture
+        ``Send(exp.batch, gather=exp.gather(op))`` instead);
+        ``Stats()["runtime"]["scatter"]`` counts asks, questions, rows and oob."""
+        if self._rt is None:
+            raise RuntimeError("Client.Ask needs the cluster's device runtime (Join with a gpu: section)")
+        return self._rt.ask(self.service, questions, scatter, op=op, sentinel=sentinel, router=self._replica_router(),
+                            **kw)
+
     def Flush(self) -> None:
         """Every earlier ``Send``'s replies final (pending re-sends run now)."""
         if self._rt is not None:
@@ -339,7 +359,7 @@ class Client:
     def ConnectionErrs(self) -> ErrChannel:
         return self._c.connection_errs()
 
-    call, go, send, tell, close, flush = Call, Go, Send, Tell, Close, Flush
+    call, go, send, tell, close, flush, ask = Call, Go, Send, Tell, Close, Flush, Ask
 
     @property
     def conns_updated(self) -> IntChannel:

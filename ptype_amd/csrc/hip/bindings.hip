@@ -15,6 +15,7 @@
 #include "breaker.hpp"
 #include "ipc_comm.hpp"
 #include "gather.hpp"
+#include "scatter.hpp"
 #include "ledger.hpp"
 #include "limit.hpp"
 #include "mailbox.hpp"
@@ -144,6 +145,13 @@ void launch_limit_clear(uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t);
 int64_t reply_gather_tile();
 void launch_reply_gather(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int, uintptr_t, uintptr_t, uintptr_t,
                          uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
+int64_t scatter_question_tile();
+int64_t scatter_expand_tile();
+void launch_scatter_count(int, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t,
+                          uintptr_t, int64_t, uintptr_t, uintptr_t);
+void launch_scatter_expand(int, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int64_t, int64_t, bool,
+                           int64_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t,
+                           uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
 }  // namespace ptype
 
 using namespace ptype;
@@ -449,6 +457,32 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("n_ok"), py::arg("count"), py::arg("bad_row"), py::arg("oob"), py::arg("stream"),
         "the M replies folded into G groups (op: index into reply_gather_limits()['ops']): the gather kernel, then the "
         "finish kernel that writes the outputs and re-arms acc ((G + 1) * acc_words u64 holding the identities)");
+
+  // ---- call scatter (scatter.hip, scatter.hpp): Q questions expanded into the T calls of one Send
+  m.def("scatter_question_tile", &scatter_question_tile, "questions per tile of the count pass");
+  m.def("scatter_expand_tile", &scatter_expand_tile, "output rows per tile of the expand pass");
+  m.def("scatter_limits", []() {
+    py::dict d;
+    d["max_rows"] = kScatterMaxRows;
+    d["max_questions"] = kScatterMaxQuestions;
+    d["max_step"] = kScatterMaxStep;
+    d["ctr_words"] = kScatterCtrWords;
+    d["rules"] = py::make_tuple("ranges", "members");
+    return d;
+  }, "the constants of scatter.hpp: the most rows and questions of one expansion, the largest step, the counter words");
+  m.def("scatter_count", &launch_scatter_count, py::arg("rule"), py::arg("q_actor"), py::arg("q_a0"), py::arg("Q"),
+        py::arg("step"), py::arg("offsets"), py::arg("G"), py::arg("n"), py::arg("first"), py::arg("tsum"),
+        py::arg("toob"), py::arg("tile_cap"), py::arg("ctr"), py::arg("stream"),
+        "the count, scan and first launches: n[q], first[q] (the exclusive prefix of n) and ctr = [total, saturating; "
+        "oob]; the host reads ctr before scatter_expand");
+  m.def("scatter_expand", &launch_scatter_expand, py::arg("rule"), py::arg("q_actor"), py::arg("q_a0"), py::arg("q_a1"),
+        py::arg("q_a2"), py::arg("q_method"), py::arg("Q"), py::arg("step"), py::arg("n_actors"), py::arg("actor_base"),
+        py::arg("has_lo"), py::arg("first_lo"), py::arg("offsets"), py::arg("members"), py::arg("G"),
+        py::arg("n_members"), py::arg("first"), py::arg("n"), py::arg("total"), py::arg("capacity"),
+        py::arg("out_actor"), py::arg("out_a0"), py::arg("out_a1"), py::arg("out_a2"), py::arg("out_method"),
+        py::arg("out_group"), py::arg("stream"),
+        "the expand launch over what scatter_count left: the `total` rows of the batch columns and of group (the "
+        "question index), 1 <= total <= capacity");
 
   // ---- circuit breaker (breaker.hip, breaker.hpp): failing actors not sent to, per actor, across Sends
   m.def("breaker_tile", &breaker_tile, "messages per tile of the breaker's streaming kernels");

@@ -1,0 +1,33 @@
+// Call scatter (scatter.hip, ops/scatter.py): Q questions expanded into T calls on the
+// device -- the scatter half of a scatter-gather (the reference's splitWork,
+// example/optimus/coordinator.go:67-73, for any step, and a broadcast to a group).
+//
+// Question q becomes n[q] >= 0 rows; first[q] is the exclusive prefix of n, so q owns
+// the rows first[q] .. first[q] + n[q] - 1, in question order.  With k = row - first[q]:
+//   ranges   t = a0[q]; n = t <= 0 ? 0 : (t - 1) / step + 1 (unsigned);
+//            actor = (actor_base + row) % n_actors, a0 = k * step (first_lo at k == 0
+//            when one is given), a1 = (k + 1) * step, a2 = t
+//   members  g = actor[q] names a group of the CSR (offsets int64[G + 1], members
+//            int32[offsets[G]]); n = offsets[g + 1] - offsets[g], 0 for g outside [0, G)
+//            (counted in `oob`); actor = members[offsets[g] + k], a0 / a1 / a2 the question's
+// The method is the question's (one id, or an int16 column copied per row); `group`
+// holds the question index of every row.
+//
+// Counters (u64): [0] the total, saturating at 2^64 - 1; [1] oob.  The host reads
+// both before the expand pass is launched, so no row is written past the capacity.
+#pragma once
+#include <stdint.h>
+
+namespace ptype {
+
+constexpr int kScatterRanges = 0;
+constexpr int kScatterMembers = 1;
+constexpr int kScatterRules = 2;
+
+constexpr int kScatterCtrWords = 2;
+// rows of one expansion: a Gather takes M < 2^31 - 1 replies
+constexpr int64_t kScatterMaxRows = 0x7ffffffell;
+constexpr int64_t kScatterMaxQuestions = 1ll << 26;
+constexpr int64_t kScatterMaxStep = 0x7fffffffll;
+
+}  // namespace ptype

@@ -169,6 +169,26 @@ def check_device(runtime, target: int) -> int:
     return int(ans[0])
 
 
+def ask_device(runtime, targets: torch.Tensor):
+    """Any targets, any time: ``splitWork`` on the device (``Scatter.ranges(10, ..,
+    first_lo=2)``), one Send, ``watchReplies`` as the ``first_ne`` gather against the
+    targets -- ``(answer int64[T], status int32[T])`` as ``FanOut.gather`` returns them,
+    without a ``FanOut`` built beforehand.  The Scatter (and its buffers, sized for one
+    Send of the runtime) is kept on the runtime."""
+    from ..ops.scatter import Scatter
+
+    runtime.host(SERVICE)
+    tg = targets.to(device=runtime.device, dtype=torch.int64).reshape(-1).contiguous()
+    sc = getattr(runtime, "_prime_scatter", None)
+    if sc is None or sc.n_actors != runtime.total_actors:
+        sc = runtime._prime_scatter = Scatter.ranges(CHUNK, runtime.total_actors, first_lo=2,
+                                                     capacity=runtime.max_batch)
+    questions = MsgBatch(torch.zeros(tg.numel(), dtype=torch.int32, device=runtime.device), tg, None, None,
+                         METHOD_PRIME_CHECK)
+    ans = runtime.ask(SERVICE, questions, sc, op="first_ne", sentinel=tg)
+    return ans.value, ans.status
+
+
 class Coordinator:
     """HTTP front end: POST /test target=<int> -> decimal answer (coordinator.go:42-65)."""
 

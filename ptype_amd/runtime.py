@@ -176,6 +176,8 @@ class DeviceRuntime:
             raise ValueError("limit_actors must be >= 0 (0: every actor of the service)")
         LimiterRef("cpu", 1, self.limit_rate, self.limit_burst)  # (validates the settings)
         self._limiter = None
+        # Scatter-gather (ask, ops/scatter.py): host counters, from what every expansion read
+        self._scatter_counters = {"asks": 0, "questions": 0, "rows": 0, "oob": 0}
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -589,6 +591,47 @@ class DeviceRuntime:
         if gather is not None:
             gather.reduce(out[0], out[1])
         return out
+
+    def ask(self, service: str | None, questions: B.MsgBatch, scatter, op: str = "sum", sentinel=None, **send_kw):
+        """Scatter-gather in one call (the optimus coordinator's ``splitWork`` ..
+        ``watchReplies``, coordinator.go:67-98): ``scatter`` (an ``ops.scatter.Scatter``)
+        expands the Q ``questions`` into T calls on the device, the calls go through
+        ``send`` -- ``send_kw`` is its keywords, so ``retries``, ``coalesce``, ``cache``,
+        ``breaker``, ``limit``, ``account``, ``router`` and ``resend_overflow`` apply to the
+        expanded calls exactly as to any batch -- and the expansion's ``Gather`` folds the
+        replies with ``op`` (``sentinel`` for ``first_ne``) into one answer per question.
+        Returns an ``ops.scatter.Answer``.  The expansion reads its total on the host, so
+        an Ask is refused under graph capture; more calls than a Send takes raise the
+        Send's error before anything travels.  Each rank expands its own questions, there
+        is no new collective: a rank whose expansion is empty joins the Send with an
+        empty batch, and at world 1 an empty expansion skips the Send."""
+        from .ops.scatter import Answer
+
+        if "gather" in send_kw:
+            raise ValueError("ask: the gather is the expansion's own (op=, sentinel=)")
+        if self._exchange is not None and self._exchange._capturing:
+            raise ValueError("ask inside a captured Send: the total of the expansion is read on the host")
+        exp = scatter.expand(questions)
+        c = self._scatter_counters
+        c["asks"] += 1
+        c["questions"] += exp.Q
+        c["rows"] += exp.total
+        c["oob"] += exp.oob
+        ex = self.exchange
+        if exp.total > ex.max_chunk * ex.chunks:
+            raise ValueError(f"batch of {exp.total} exceeds max_batch {ex.max_chunk * ex.chunks}")
+        g = exp.gather(op, sentinel) if exp.Q else None
+        if exp.total or self.world > 1:
+            out = self.send(service, exp.batch, gather=g, **send_kw)
+        else:
+            out = (torch.empty(0, dtype=torch.int64, device=self.device),
+                   torch.empty(0, dtype=torch.int32, device=self.device))
+            if g is not None:
+                g.reduce(out[0], out[1])
+        if g is None:
+            e64, e32 = exp.first, exp.n  # (no questions: empty int64 and int32 tensors)
+            return Answer(e64, e32, e32, e32, e32, exp.first, exp.n, exp.oob, out[0], out[1])
+        return Answer(g.value, g.status, g.n_ok, g.count, g.bad_row, exp.first, exp.n, exp.oob, out[0], out[1])
 
     def cache_clear(self) -> None:
         """Drop every entry of the reply cache (O(1): the cache's epoch moves on)."""
@@ -1073,6 +1116,7 @@ class DeviceRuntime:
         else:
             out["limit"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "throttled": 0, "oob": 0, "actors": 0,
                             "rate": 0, "burst": 0}
+        out["scatter"] = dict(self._scatter_counters)
         return out
 
     def close(self) -> None:
