@@ -208,7 +208,10 @@ static RpcHandler device_handler(uintptr_t fn, uintptr_t ctx, int method, uint32
   return [submit, ctx, method, actor, fields, actor_field](const gob::Value& args) -> gob::Value {
     const MsgRecord m = encode_device_call(args, method, actor, fields, actor_field);
     ReplyRecord r{};
-    if (submit((void*)ctx, &m, &r, 1) != 0) fail(Errc::kRpc, "device dispatcher unavailable");
+    if (m.actor == kNoActor)  // an actor field out of range: answered here, no handler runs (records.hpp)
+      r.status = kStatusNoActor;
+    else if (submit((void*)ctx, &m, &r, 1) != 0)
+      fail(Errc::kRpc, "device dispatcher unavailable");
     RpcOutcome o = device_outcome(r);
     if (!o.ok()) fail(o.code, o.error);
     return o.reply;

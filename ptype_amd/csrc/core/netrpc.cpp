@@ -480,7 +480,7 @@ int host_batch_multiply(void* ctx, const uint8_t* bytes, const int64_t* offsets,
     } else if (!gob_get_uint(p, end, &tid) || gob_unzz(tid) != type_id) {
       st = 2;
     } else {
-      int field = -1;
+      int64_t field = -1;
       for (;;) {
         uint64_t delta, u;
         if (!gob_get_uint(p, end, &delta)) {
@@ -488,9 +488,14 @@ int host_batch_multiply(void* ctx, const uint8_t* bytes, const int64_t* offsets,
           break;
         }
         if (delta == 0) break;
-        field += (int)delta;
-        if (field >= nf || field >= 8 || !gob_get_uint(p, end, &u)) {
+        // the delta is network input: bounded as a u64 before it moves the index
+        if (delta > 8 || field + (int64_t)delta >= nf || field + (int64_t)delta >= 8) {
           st = 3;
+          break;
+        }
+        field += (int64_t)delta;
+        if (!gob_get_uint(p, end, &u)) {
+          st = 1;
           break;
         }
         v[field] = gob_unzz(u);
@@ -498,7 +503,8 @@ int host_batch_multiply(void* ctx, const uint8_t* bytes, const int64_t* offsets,
       if (st == 0 && p != end) st = 4;
     }
     gob_status[i] = st;
-    const int64_t a = field_col[0] >= 0 ? v[field_col[0]] : 0, b = field_col[1] >= 0 ? v[field_col[1]] : 0;
+    auto arg = [&](int k) { return st == 0 && field_col[k] >= 0 && field_col[k] < 8 ? v[field_col[k]] : 0; };
+    const int64_t a = arg(0), b = arg(1);
     out[i].value = (int64_t)((uint64_t)a * (uint64_t)b);
     out[i].status = kStatusOk;
     out[i].actor = 0;
@@ -558,7 +564,8 @@ MsgRecord encode_device_call(const gob::Value& args, int method, uint32_t actor,
       if (f) a[k] = f->kind == gob::kUint ? (int64_t)f->u : f->i;
     }
     if (!actor_field.empty())
-      if (const gob::Value* f = args.field(actor_field)) m.actor = (uint32_t)(f->kind == gob::kUint ? f->u : f->i);
+      if (const gob::Value* f = args.field(actor_field))  // a uint past int64 is out of range like any other
+        m.actor = f->kind == gob::kUint ? (f->u >= kNoActor ? kNoActor : (uint32_t)f->u) : actor_of_field(f->i);
   } else if (args.kind == gob::kInt) {
     a[0] = args.i;
   }
@@ -629,6 +636,11 @@ RpcOutcome ShmRpcConn::call(const std::string& method, const gob::Value& args, i
   }
   if (const DevMethod* dm = device_method(method)) {
     const MsgRecord m = encode_device_call(args, (int)dm->method, dm->actor, dm->fields, dm->actor_field);
+    if (m.actor == kNoActor) {  // an actor field out of range: answered here, no handler runs (records.hpp)
+      ReplyRecord r{};
+      r.status = kStatusNoActor;
+      return device_outcome(r);
+    }
     try {
       const ReplyRecord r = shm_call(view_, m, timeout_ms < 0 ? 30.0 : timeout_ms / 1e3);
       shm_calls_.fetch_add(1);

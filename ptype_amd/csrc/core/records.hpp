@@ -62,6 +62,13 @@ inline constexpr bool method_stateless(uint32_t m) {
   return m == kCalculatorMultiply || m == kPrimeCheck || m == kEcho;
 }
 
+// The actor id that names no actor.  A request's actor field is an int64 on the
+// wire: one outside [0, kNoActor) names no actor -- never the actor its low 32
+// bits would spell (2^32 + 3 is not actor 3) -- and is answered kStatusNoActor
+// with no handler run (the gob bridge's actor column and encode_device_call).
+constexpr uint32_t kNoActor = 0xffffffffu;
+inline constexpr uint32_t actor_of_field(int64_t v) { return (uint64_t)v >= kNoActor ? kNoActor : (uint32_t)v; }
+
 enum RecordFlags : uint16_t {
   kFlagValid = 1,
   kFlagRouted = 2,  // `actor` holds the destination's local mailbox index

@@ -267,12 +267,12 @@ int64_t gob_ws_words(int64_t M) {
 
 void launch_gob_encode(const std::vector<uintptr_t>& cols, int64_t M, uint32_t type_id, uintptr_t out,
                        uintptr_t offsets, uintptr_t ws, uintptr_t stream) {
-  const GobCols c = gob_cols(cols);
   hipStream_t s = as_stream(stream);
-  if (M <= 0) {
+  if (M <= 0) {  // (an empty column has no address: nothing to check)
     PT_HIP_CHECK(hipMemsetAsync((void*)offsets, 0, sizeof(int64_t), s));
     return;
   }
+  const GobCols c = gob_cols(cols);
   if (M >= (1ll << 31)) throw std::invalid_argument("gob encode: at most 2^31 messages");
   const int64_t G = (M + kGobTile - 1) / kGobTile;
   unsigned* block_bytes = (unsigned*)ws;
@@ -286,8 +286,8 @@ void launch_gob_encode(const std::vector<uintptr_t>& cols, int64_t M, uint32_t t
 
 void launch_gob_decode(uintptr_t buf, uintptr_t offsets, int64_t M, uint32_t type_id, const std::vector<uintptr_t>& cols,
                        uintptr_t status, uintptr_t stream) {
-  const GobCols c = gob_cols(cols);
   if (M <= 0) return;
+  const GobCols c = gob_cols(cols);
   int64_t g = (M + 255) / 256;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(gob_decode_kernel, dim3((unsigned)g), dim3(256), 0, as_stream(stream), (const uint8_t*)buf,

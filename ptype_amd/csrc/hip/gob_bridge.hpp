@@ -32,12 +32,15 @@ void launch_gob_decode(uintptr_t buf, uintptr_t offsets, int64_t M, uint32_t typ
 // actor[i] = the actor field's column (or the fixed actor); a message that failed
 // to decode (gob status != 0) gets no actor (0xffffffff): it is answered
 // no-actor by the enqueue and never runs a handler -- the client is told
-// "decoding error", so a stateful method must not have changed state for it
+// "decoding error", so a stateful method must not have changed state for it.
+// An actor field is an int64 on the wire and an actor id is a u32 below
+// 0xffffffff: a field outside [0, 2^32 - 1) names no actor either (never its low
+// 32 bits -- actor 2^32 + 3 is not actor 3), as in encode_device_call
 __global__ __launch_bounds__(256) void gob_bridge_actor_kernel(const int64_t* __restrict__ col, uint32_t fixed,
                                                                const int32_t* __restrict__ gst, int64_t n,
                                                                uint32_t* __restrict__ actor) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    actor[i] = gst[i] != 0 ? 0xffffffffu : col ? (uint32_t)col[i] : fixed;
+    actor[i] = gst[i] != 0 ? 0xffffffffu : col ? actor_of_field(col[i]) : fixed;
 }
 
 class GobBridge {

@@ -123,39 +123,64 @@ def encode_structs_ref(cols: list[torch.Tensor], type_id: int):
     return torch.tensor(list(b"".join(msgs)), dtype=torch.uint8), torch.tensor(offs, dtype=torch.int64)
 
 
+def _read_uint(b: bytes, pos: int, end: int):
+    """Strict ``uint`` read inside ``b[pos:end]``: ``(value, next pos)``, or None on
+    no bytes left, a count byte meaning more than 8 bytes, or fewer bytes left
+    than the count (gob_get_uint of csrc/hip/gob.hip)."""
+    if pos >= end:
+        return None
+    c = b[pos]
+    if c < 128:
+        return c, pos + 1
+    n = 256 - c
+    if n > 8 or end - (pos + 1) < n:
+        return None
+    return int.from_bytes(b[pos + 1:pos + 1 + n], "big"), pos + 1 + n
+
+
+def _unzz(u: int) -> int:
+    return -((u >> 1) + 1) if u & 1 else u >> 1
+
+
+def _parse_ref(data: bytes, lo: int, hi: int, nf: int, type_id: int):
+    """One message: (status, {field: value}); the kernel's rules in its order."""
+    r = _read_uint(data, lo, hi)
+    if r is None or hi - r[1] != r[0]:
+        return STATUS_TRUNCATED, {}
+    r = _read_uint(data, r[1], hi)
+    if r is None or _unzz(r[0]) != type_id:
+        return STATUS_WRONG_TYPE, {}
+    p, field, vals = r[1], -1, {}
+    while True:
+        r = _read_uint(data, p, hi)
+        if r is None:
+            return STATUS_TRUNCATED, {}
+        d, p = r
+        if d == 0:
+            break
+        if d > MAX_FIELDS or field + d >= nf:
+            return STATUS_BAD_FIELD, {}
+        field += d
+        r = _read_uint(data, p, hi)
+        if r is None:
+            return STATUS_TRUNCATED, {}
+        vals[field] = _unzz(r[0])
+        p = r[1]
+    if p != hi:
+        return STATUS_TRAILING, {}
+    return STATUS_OK, vals
+
+
 def decode_structs_ref(buf: torch.Tensor, offsets: torch.Tensor, nf: int, type_id: int):
-    """Per-message parse on the host (the same rules as the kernel)."""
+    """Per-message parse on the host (the same rules as the kernel): never raises
+    on malformed bytes; a message that is not OK decodes to zeros."""
     data = bytes(buf.tolist())
     offs = offsets.tolist()
     M = len(offs) - 1
     cols = [[0] * M for _ in range(nf)]
     status = [STATUS_OK] * M
     for i in range(M):
-        lo, hi = offs[i], offs[i + 1]
-        try:
-            n, p = _get_uint(data[:hi], lo)
-            if hi - p != n:
-                raise IndexError
-            t, p = _get_uint(data[:hi], p)
-            if (-((t >> 1) + 1) if t & 1 else t >> 1) != type_id:
-                status[i] = STATUS_WRONG_TYPE
-                continue
-            field, vals = -1, {}
-            while True:
-                d, p = _get_uint(data[:hi], p)
-                if d == 0:
-                    break
-                field += d
-                if field >= nf:
-                    status[i] = STATUS_BAD_FIELD
-                    break
-                u, p = _get_uint(data[:hi], p)
-                vals[field] = -((u >> 1) + 1) if u & 1 else u >> 1
-            if status[i] == STATUS_OK and p != hi:
-                status[i] = STATUS_TRAILING
-            if status[i] == STATUS_OK:
-                for f, v in vals.items():
-                    cols[f][i] = v
-        except IndexError:
-            status[i] = STATUS_TRUNCATED
+        status[i], vals = _parse_ref(data, offs[i], offs[i + 1], nf, type_id)
+        for f, v in vals.items():
+            cols[f][i] = v
     return [torch.tensor(c, dtype=torch.int64) for c in cols], torch.tensor(status, dtype=torch.int32)

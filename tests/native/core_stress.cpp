@@ -6,9 +6,10 @@
 // sanitizer runtime owns the process: concurrent channels, a 3-member Raft
 // cluster with concurrent clients, watches, leases and a leader failover, the
 // net/rpc server with a balancer-driven client under concurrent Call/Go, and
-// the Cluster facade (Join -> register -> watch -> NewClient -> Call -> Close).
+// the Cluster facade (Join -> register -> watch -> NewClient -> Call -> Close),
+// and the host gob parser on malformed network input.
 //
-// usage: core_stress <workdir> [channel|raft|rpc|api|learner ...]   (default: all)
+// usage: core_stress <workdir> [channel|raft|rpc|api|learner|gobparse ...]   (default: all)
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <sys/socket.h>
@@ -464,6 +465,66 @@ void scenario_commcell() {
   }
 }
 
+// The host parser of gob value messages (host_batch_multiply, csrc/core/netrpc.cpp)
+// on malformed network input, a dozen messages of the corpus of tests/_gob_spec.py
+// as literal bytes: a field delta is a u64 on the wire, and one past 2^31 once
+// moved the parser's index below its value array (a stack write the sanitizer
+// reports); statuses are the kernel's (csrc/hip/gob.hip GobStatus).  Then the
+// actor-id range of encode_device_call: a field outside [0, 2^32 - 1) names no actor.
+void scenario_gobparse() {
+  struct Case {
+    std::vector<uint8_t> msg;
+    int32_t status;
+    int64_t product;
+  };
+  const std::vector<Case> cases = {
+      {{0x07, 0xff, 0x82, 0x01, 0x0e, 0x01, 0x10, 0x00}, 0, 56},                                // Args{7, 8}
+      {{0x09, 0xff, 0x82, 0xfc, 0xff, 0xff, 0xff, 0xff, 0x0e, 0x00}, 3, 0},                     // delta 0xFFFFFFFF
+      {{0x09, 0xff, 0x82, 0xfc, 0x80, 0x00, 0x00, 0x00, 0x0e, 0x00}, 3, 0},                     // delta 2^31
+      {{0x0a, 0xff, 0x82, 0xfb, 0x01, 0x00, 0x00, 0x00, 0x00, 0x0e, 0x00}, 3, 0},               // delta 2^32
+      {{0x0a, 0xff, 0x82, 0xfb, 0x01, 0x00, 0x00, 0x00, 0x01, 0x0e, 0x00}, 3, 0},               // delta 2^32 + 1
+      {{0x0d, 0xff, 0x82, 0xf8, 0x80, 0, 0, 0, 0, 0, 0, 0, 0x0e, 0x00}, 3, 0},                  // delta 2^63
+      {{0x0d, 0xff, 0x82, 0xf8, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0x0e, 0x00}, 3, 0},  // 2^64 - 1
+      {{0x05, 0xff, 0x82, 0x09, 0x0e, 0x00}, 3, 0},                                             // delta 9
+      {{0x05, 0xff, 0x82, 0x03, 0x0e, 0x00}, 3, 0},                                             // field 2 of 2
+      {{0x04, 0xff, 0x82, 0x01, 0xfe}, 1, 0},                                                   // value cut short
+      {{0x0e, 0xff, 0x82, 0x01, 0xf7, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0x00}, 1, 0},                  // a 9-byte value
+      {{0x03, 0xff, 0x84, 0x00}, 2, 0},                                                         // type id 66
+      {{0x06, 0xff, 0x82, 0x01, 0x0e, 0x00, 0x00}, 4, 0},                                       // trailing byte
+      {{0x05, 0xff, 0x82, 0x02, 0x0e, 0x00}, 0, 0},                                             // Args{0, 7}
+      {{0x04, 0xff, 0x82}, 1, 0},                                                               // ends early, last
+  };
+  // the batch in a heap buffer of exactly its size: a read past its end is reported too
+  std::vector<int64_t> offsets{0};
+  size_t total = 0;
+  for (const auto& c : cases) offsets.push_back((int64_t)(total += c.msg.size()));
+  std::unique_ptr<uint8_t[]> bytes(new uint8_t[total]);
+  for (size_t i = 0; i < cases.size(); ++i) std::memcpy(bytes.get() + offsets[i], cases[i].msg.data(), cases[i].msg.size());
+  const int32_t col[4] = {0, 1, -1, -1};
+  std::vector<int32_t> gst(cases.size(), -1);
+  std::vector<ReplyRecord> rep(cases.size());
+  CHECK(host_batch_multiply(nullptr, bytes.get(), offsets.data(), (int64_t)cases.size(), 65, 2, col, gst.data(),
+                            rep.data()) == 0);
+  for (size_t i = 0; i < cases.size(); ++i) {
+    if (gst[i] != cases[i].status || rep[i].value != cases[i].product)
+      std::fprintf(stderr, "gobparse: message %zu: status %d value %lld\n", i, gst[i], (long long)rep[i].value);
+    CHECK(gst[i] == cases[i].status);
+    CHECK(rep[i].value == cases[i].product);
+  }
+  auto actor_of = [](gob::Value id) {
+    gob::Value args = gob::Value::Struct("Args");
+    args.fields = {{"A", gob::Value::Int(5)}, {"Id", std::move(id)}};
+    return encode_device_call(args, kCounterAdd, 7, {"A"}, "Id").actor;
+  };
+  CHECK(actor_of(gob::Value::Int(3)) == 3u);
+  CHECK(actor_of(gob::Value::Int(0xfffffffell)) == 0xfffffffeu);
+  CHECK(actor_of(gob::Value::Uint(0xfffffffeull)) == 0xfffffffeu);
+  for (int64_t id : {(int64_t)-1, (int64_t)0xffffffffll, (int64_t)1 << 32, ((int64_t)1 << 32) + 3, INT64_MAX, INT64_MIN})
+    CHECK(actor_of(gob::Value::Int(id)) == kNoActor);
+  for (uint64_t id : {(uint64_t)0xffffffffull, ((uint64_t)1 << 32) + 3, (uint64_t)1 << 63, ~(uint64_t)0})
+    CHECK(actor_of(gob::Value::Uint(id)) == kNoActor);
+}
+
 // Elastic scale-out: a second member joins as a learner through the first one's
 // client URL and is promoted once caught up (cluster/cluster.go:105-147, :183-195).
 void scenario_learner(const std::string& dir) {
@@ -503,7 +564,7 @@ int main(int argc, char** argv) {
   }
   const std::string dir = argv[1];
   std::vector<std::string> want(argv + 2, argv + argc);
-  if (want.empty()) want = {"channel", "raft", "rpc", "api", "learner", "shm", "commcell"};
+  if (want.empty()) want = {"channel", "raft", "rpc", "api", "learner", "shm", "commcell", "gobparse"};
   std::map<std::string, std::function<void()>> all = {
       {"channel", [] { scenario_channel(); }},
       {"raft", [&] { scenario_raft(dir); }},
@@ -512,6 +573,7 @@ int main(int argc, char** argv) {
       {"learner", [&] { scenario_learner(dir); }},
       {"shm", [] { scenario_shm(); }},
       {"commcell", [] { scenario_commcell(); }},
+      {"gobparse", [] { scenario_gobparse(); }},
   };
   for (const auto& w : want) {
     auto it = all.find(w);
