@@ -114,7 +114,6 @@ int64_t ledger_tile();
 void launch_ledger_account(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t,
                            uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
 int64_t coalesce_tile();
-int64_t coalesce_select_tile();
 void launch_coalesce_group(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int,
                            uintptr_t, uintptr_t);
 void launch_coalesce_select(uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
@@ -396,7 +395,6 @@ PYBIND11_MODULE(_hip, m) {
 
   // ---- Send coalescing (coalesce.hip, coalesce.hpp): duplicates of a pure call are sent once
   m.def("coalesce_tile", &coalesce_tile, "messages per block of coalesce_group's insert kernel");
-  m.def("coalesce_select_tile", &coalesce_select_tile, "messages per block of coalesce_select");
   m.def("coalesce_pure", [](uint32_t method) { return method_pure(method & 0xffffu); }, py::arg("method"),
         "whether duplicates of this method are coalesced (coalesce.hpp)");
   m.def("coalesce_hash", [](uint32_t actor, uint32_t method, int64_t a0, int64_t a1, int64_t a2) {
@@ -412,7 +410,7 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("a0_out"), py::arg("a1_out"), py::arg("a2_out"), py::arg("method_out"), py::arg("counts"),
         py::arg("k_out"), py::arg("stream"),
         "stable compaction of the messages with lead[i] == i: idx (ascending), the gathered rows of every non-null "
-        "column, pos[i] = i's row (-1 for a follower), K in k_out[0]; counts: ceil(M / coalesce_select_tile()) u32");
+        "column, pos[i] = i's row (-1 for a follower), K in k_out[0]; counts: ceil(M / retry_tile()) u32");
   m.def("coalesce_fanout", &launch_coalesce_fanout, py::arg("val"), py::arg("st"), py::arg("M"), py::arg("lead"),
         py::arg("pos"), py::arg("v2"), py::arg("s2"), py::arg("K"), py::arg("stream"),
         "val[i] = v2[pos[lead[i]]], st[i] = s2[pos[lead[i]]] for i < M");

@@ -33,9 +33,7 @@ constexpr uint64_t kBreakerObsOk = 1ull << 63;
 constexpr uint32_t kBreakerMaxTick = 0x7fffffffu;
 constexpr int64_t kBreakerMaxActors = 1ll << 28;
 
-// What the admit pass leaves in st[i] for a row that travels: a status no handler returns,
-// selected by retry_select's raw mask (the reply cache's marker, reply_cache.hpp).
-constexpr int kBreakerPending = 31;
+constexpr int kBreakerPending = kPending;  // what the admit pass leaves in st[i] for a row that travels
 
 enum BreakerCounter {
   kBreakerNOpen = 0,    // words with bit 63 set

@@ -11,10 +11,9 @@
 //                            lowest index
 //   coalesce_lead_kernel     launch 2: every message re-walks its probe chain and reads
 //                            its class's slot: lead[i]; a non-pure message gets lead[i] = i
-//   coalesce_count_kernel /  stable compaction of the messages with lead[i] == i, as
-//   coalesce_select_kernel   retry.hip compacts by status (per-tile counts, ballot +
-//                            mbcnt ranks, no atomics): idx, the gathered columns, K and
-//                            pos[i] = i's row in the sub-batch (-1 for a follower)
+//   compact.hpp              stable compaction of the messages with lead[i] == i (the one
+//                            retry.hip compacts by status with): idx, the gathered columns,
+//                            K and pos[i] = i's row in the sub-batch (-1 for a follower)
 //   coalesce_fanout_kernel   val[i] = v2[pos[lead[i]]], st[i] = s2[pos[lead[i]]]
 //
 // Why the table is exact and deterministic.  A slot is claimed by a compare-and-swap
@@ -45,6 +44,7 @@
 // whose index a slot holds inserts its key into HBM: an all-identical batch costs one
 // global atomic per block.
 #include "coalesce.hpp"
+#include "compact.hpp"
 
 namespace ptype {
 
@@ -195,132 +195,7 @@ __global__ __launch_bounds__(kCoThreads) void coalesce_lead_kernel(CoIn in, cons
   lead[i] = (int)l;
 }
 
-// ---------------------------------------------------------------- leader selection (retry.hip's compaction, by lead[i] == i)
-constexpr int kSelThreads = 256;
-constexpr int kSelWaves = kSelThreads / kWave;
-constexpr int kSelLoads = 4;                                 // dwordx4 loads per thread
-constexpr int kSelSegs = kSelLoads * kSelWaves;              // 256-element segments per tile
-constexpr int kSelTile = kSelThreads * kSelLoads * 4;        // 4096 messages
-
-// lead[i .. i + 4) (i a multiple of 4; `lead` 16-byte aligned).  Past M: -1, no leader.
-__device__ __forceinline__ int4 sel_load4(const int* __restrict__ lead, int64_t i, int64_t M) {
-  if (i + 4 <= M) return *reinterpret_cast<const int4*>(lead + i);
-  int4 v = {-1, -1, -1, -1};
-  if (i < M) v.x = lead[i];
-  if (i + 1 < M) v.y = lead[i + 1];
-  if (i + 2 < M) v.z = lead[i + 2];
-  return v;
-}
-
-__device__ __forceinline__ int64_t sel_elem(int64_t tile, int j, unsigned wave, unsigned lane) {
-  return tile * kSelTile + (int64_t)(j * kSelWaves + (int)wave) * (kWave * 4) + lane * 4;
-}
-
-__global__ __launch_bounds__(kSelThreads) void coalesce_count_kernel(const int* __restrict__ lead, int64_t M,
-                                                                      uint32_t* __restrict__ counts) {
-  __shared__ unsigned wave_cnt[kSelWaves];
-  const unsigned lane = lane_id(), wave = threadIdx.x / kWave;
-  const int64_t tile = blockIdx.x;
-  unsigned n = 0;  // wave-uniform: every term is a popcount of a ballot
-#pragma unroll
-  for (int j = 0; j < kSelLoads; ++j) {
-    const int64_t i = sel_elem(tile, j, wave, lane);
-    const int4 v = sel_load4(lead, i, M);
-    n += __popcll(__ballot(v.x == (int)i)) + __popcll(__ballot(v.y == (int)i + 1)) +
-         __popcll(__ballot(v.z == (int)i + 2)) + __popcll(__ballot(v.w == (int)i + 3));
-  }
-  if (lane == 0) wave_cnt[wave] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-#pragma unroll
-    for (int w = 0; w < kSelWaves; ++w) t += wave_cnt[w];
-    counts[tile] = t;
-  }
-}
-
-__global__ __launch_bounds__(kSelThreads) void coalesce_select_kernel(
-    const int* __restrict__ lead, int64_t M, const uint32_t* __restrict__ counts, const int* __restrict__ actor,
-    const int64_t* __restrict__ a0, const int64_t* __restrict__ a1, const int64_t* __restrict__ a2,
-    const int16_t* __restrict__ method, int* __restrict__ idx, int* __restrict__ pos, int* __restrict__ actor_o,
-    int64_t* __restrict__ a0_o, int64_t* __restrict__ a1_o, int64_t* __restrict__ a2_o, int16_t* __restrict__ method_o,
-    int* __restrict__ k_out) {
-  __shared__ unsigned wave_sum[kSelWaves];
-  __shared__ unsigned seg_cnt[kSelSegs];
-  __shared__ int sel[kSelTile];  // the tile's leaders, in order
-  const unsigned lane = lane_id(), wave = threadIdx.x / kWave;
-  const int64_t tile = blockIdx.x;
-
-  // this tile's first output row: the sum of the counts of the tiles below it
-  unsigned below = 0;
-  for (int64_t t = threadIdx.x; t < tile; t += kSelThreads) below += counts[t];
-  below = wave_incl_scan(below);
-  if (lane == kWave - 1) wave_sum[wave] = below;
-
-  uint64_t b[kSelLoads][4];
-#pragma unroll
-  for (int j = 0; j < kSelLoads; ++j) {
-    const int64_t i = sel_elem(tile, j, wave, lane);
-    const int4 v = sel_load4(lead, i, M);
-    b[j][0] = __ballot(v.x == (int)i);
-    b[j][1] = __ballot(v.y == (int)i + 1);
-    b[j][2] = __ballot(v.z == (int)i + 2);
-    b[j][3] = __ballot(v.w == (int)i + 3);
-    if (lane == 0)
-      seg_cnt[j * kSelWaves + wave] = __popcll(b[j][0]) + __popcll(b[j][1]) + __popcll(b[j][2]) + __popcll(b[j][3]);
-  }
-  __syncthreads();
-  unsigned off = 0;
-#pragma unroll
-  for (int w = 0; w < kSelWaves; ++w) off += wave_sum[w];
-  unsigned seg_off[kSelLoads], total = 0;
-#pragma unroll
-  for (int s = 0; s < kSelSegs; ++s) {  // (LDS broadcast reads; s = j * kSelWaves + wave)
-    if ((s % kSelWaves) == (int)wave) seg_off[s / kSelWaves] = total;
-    total += seg_cnt[s];
-  }
-#pragma unroll
-  for (int j = 0; j < kSelLoads; ++j) {
-    // leaders of lower lanes come first, then this lane's lower components
-    unsigned r = seg_off[j] + mbcnt64(b[j][0]) + mbcnt64(b[j][1]) + mbcnt64(b[j][2]) + mbcnt64(b[j][3]);
-    const int64_t i = sel_elem(tile, j, wave, lane);
-    int p[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      p[c] = -1;
-      if ((b[j][c] >> lane) & 1ull) {
-        p[c] = (int)(off + r);
-        sel[r++] = (int)i + c;
-      }
-    }
-    if (i + 4 <= M) {
-      *reinterpret_cast<int4*>(pos + i) = make_int4(p[0], p[1], p[2], p[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (i + c < M) pos[i + c] = p[c];
-    }
-  }
-  __syncthreads();
-  // consecutive threads take consecutive output rows: coalesced stores, scattered loads
-  for (unsigned k = threadIdx.x; k < total; k += kSelThreads) {
-    const int i = sel[k];
-    const int64_t o = (int64_t)off + k;
-    idx[o] = i;
-    actor_o[o] = actor[i];
-    a0_o[o] = a0[i];
-    if (a1) a1_o[o] = a1[i];
-    if (a2) a2_o[o] = a2[i];
-    if (method) method_o[o] = method[i];
-  }
-  if (tile == (int64_t)gridDim.x - 1 && threadIdx.x == 0) *k_out = (int)(off + total);
-}
-
 // ---------------------------------------------------------------- fan-out
-struct alignas(16) CoI64x2 {
-  int64_t x, y;
-};
-
 // The reply of message i's leader.  A lead or pos outside its range (never, for the
 // outputs of the kernels above) reads nothing and answers kStatusNotDelivered.
 __device__ __forceinline__ void co_fetch(int l, const int* __restrict__ pos, const int64_t* __restrict__ v2,
@@ -350,8 +225,8 @@ __global__ __launch_bounds__(256) void coalesce_fanout_kernel(int64_t* __restric
       co_fetch(l.y, pos, v2, s2, M, K, v[1], s[1]);
       co_fetch(l.z, pos, v2, s2, M, K, v[2], s[2]);
       co_fetch(l.w, pos, v2, s2, M, K, v[3], s[3]);
-      *reinterpret_cast<CoI64x2*>(val + i) = CoI64x2{v[0], v[1]};
-      *reinterpret_cast<CoI64x2*>(val + i + 2) = CoI64x2{v[2], v[3]};
+      *reinterpret_cast<I64x2*>(val + i) = I64x2{v[0], v[1]};
+      *reinterpret_cast<I64x2*>(val + i + 2) = I64x2{v[2], v[3]};
       *reinterpret_cast<int4*>(st + i) = make_int4(s[0], s[1], s[2], s[3]);
     } else {
       for (int c = 0; i + c < M; ++c) {
@@ -365,7 +240,6 @@ __global__ __launch_bounds__(256) void coalesce_fanout_kernel(int64_t* __restric
 
 // ---------------------------------------------------------------- launchers
 int64_t coalesce_tile() { return kCoTile; }
-int64_t coalesce_select_tile() { return kSelTile; }
 
 // `table`: (1 << table_log2) u32 words of workspace, at least 2 M of them; cleared here
 // by an asynchronous fill on `stream`.  actor int32 / a0..a2 int64 / method_col u16
@@ -395,7 +269,7 @@ void launch_coalesce_group(uintptr_t actor, uintptr_t method_col, uint32_t metho
   PT_HIP_CHECK(hipGetLastError());
 }
 
-// `counts`: ceil(M / coalesce_select_tile()) u32 words of workspace.  The output columns
+// `counts`: ceil(M / retry_tile()) u32 words of workspace.  The output columns
 // hold up to M rows; a null input column leaves its output alone.  lead and pos are
 // 16-byte aligned.
 void launch_coalesce_select(uintptr_t lead, int64_t M, uintptr_t actor, uintptr_t a0, uintptr_t a1, uintptr_t a2,
@@ -408,16 +282,8 @@ void launch_coalesce_select(uintptr_t lead, int64_t M, uintptr_t actor, uintptr_
   if (!lead || !actor || !a0 || !idx || !pos || !actor_o || !a0_o || !counts || !k_out || (a1 && !a1_o) ||
       (a2 && !a2_o) || (method && !method_o))
     throw std::invalid_argument("coalesce_select: null buffer");
-  hipStream_t s = as_stream(stream);
-  const unsigned tiles = (unsigned)((M + kSelTile - 1) / kSelTile);
-  hipLaunchKernelGGL(coalesce_count_kernel, dim3(tiles), dim3(kSelThreads), 0, s, (const int*)lead, M,
-                     (uint32_t*)counts);
-  PT_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(coalesce_select_kernel, dim3(tiles), dim3(kSelThreads), 0, s, (const int*)lead, M,
-                     (const uint32_t*)counts, (const int*)actor, (const int64_t*)a0, (const int64_t*)a1,
-                     (const int64_t*)a2, (const int16_t*)method, (int*)idx, (int*)pos, (int*)actor_o, (int64_t*)a0_o,
-                     (int64_t*)a1_o, (int64_t*)a2_o, (int16_t*)method_o, (int*)k_out);
-  PT_HIP_CHECK(hipGetLastError());
+  launch_compact<OwnIndex, true>(lead, M, OwnIndex{}, actor, a0, a1, a2, method, idx, pos, actor_o, a0_o, a1_o, a2_o,
+                                 method_o, counts, k_out, stream);
 }
 
 // val int64[M], st int32[M], lead int32[M]: 16-byte aligned; pos int32[M]; v2 int64[K], s2 int32[K].

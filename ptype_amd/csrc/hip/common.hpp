@@ -29,6 +29,19 @@ struct alignas(16) TableEntry {
 };
 static_assert(sizeof(TableEntry) == 16, "TableEntry must be 16 bytes");
 
+// Four int64 (as two halves) or four int16 of a column in one access.
+struct alignas(16) I64x2 {
+  int64_t x, y;
+};
+struct alignas(8) I16x4 {
+  int16_t x, y, z, w;
+};
+
+// What a Send wrapper (reply cache, breaker, limiter) leaves in st[i] for a row that still
+// has to travel: a status no handler returns, selected by retry_select's raw mask and
+// replaced by the inner Send's reply before the caller sees the outputs.
+constexpr int kPending = 31;
+
 constexpr uint64_t kKeyEmpty = 0ull;
 constexpr uint64_t kKeyTomb = ~0ull;
 

@@ -44,10 +44,6 @@ constexpr int kGatherRows = 2;                                 // 4-message rows
 constexpr int kGatherTile = kGatherThreads * kGatherRows * 4;  // 2048 messages
 constexpr uint64_t kGatherOne = (1ull << 32) | 1ull;           // one OK row in `count << 32 | n_ok`
 
-struct alignas(16) GatherI64x2 {
-  int64_t x, y;
-};
-
 // One run's partial result.
 struct GatherPart {
   uint64_t val, cnt;
@@ -95,8 +91,8 @@ __device__ __forceinline__ void gather_load4(const int* __restrict__ p, int64_t 
 template <bool ALIGNED>
 __device__ __forceinline__ void gather_load4(const int64_t* __restrict__ p, int64_t i, int64_t M, int64_t (&o)[4]) {
   if (ALIGNED && i + 4 <= M) {
-    const GatherI64x2 lo = *reinterpret_cast<const GatherI64x2*>(p + i);
-    const GatherI64x2 hi = *reinterpret_cast<const GatherI64x2*>(p + i + 2);
+    const I64x2 lo = *reinterpret_cast<const I64x2*>(p + i);
+    const I64x2 hi = *reinterpret_cast<const I64x2*>(p + i + 2);
     o[0] = lo.x, o[1] = lo.y, o[2] = hi.x, o[3] = hi.y;
     return;
   }
@@ -262,8 +258,8 @@ __global__ __launch_bounds__(kGatherThreads) void reply_gather_finish_kernel(
     int64_t* __restrict__ oob) {
   const unsigned g = blockIdx.x * kGatherThreads + threadIdx.x;
   if (g >= G) return;
-  GatherI64x2* a = reinterpret_cast<GatherI64x2*>(acc + (size_t)g * kGatherAccWords);
-  const GatherI64x2 lo = a[0], hi = a[1];
+  I64x2* a = reinterpret_cast<I64x2*>(acc + (size_t)g * kGatherAccWords);
+  const I64x2 lo = a[0], hi = a[1];
   const uint64_t cnt = (uint64_t)lo.y;
   uint32_t bad = (uint32_t)(uint64_t)hi.x;
   const uint32_t hit = (uint32_t)((uint64_t)hi.x >> 32);
@@ -280,8 +276,8 @@ __global__ __launch_bounds__(kGatherThreads) void reply_gather_finish_kernel(
   bad_row[g] = bad != kGatherNoRow ? (int)bad : -1;
   n_ok[g] = (int)(uint32_t)cnt;
   count[g] = (int)(cnt >> 32);
-  a[0] = GatherI64x2{identity, 0};
-  a[1] = GatherI64x2{-1, 0};
+  a[0] = I64x2{identity, 0};
+  a[1] = I64x2{-1, 0};
   if (g == 0) {
     oob[0] = (int64_t)acc[(size_t)G * kGatherAccWords];
     acc[(size_t)G * kGatherAccWords] = 0;

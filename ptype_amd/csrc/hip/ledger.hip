@@ -44,13 +44,6 @@ constexpr int kLedgerSlotBits = 11;
 constexpr int kLedgerSlots = 1 << kLedgerSlotBits;                 // LDS combine table: 16 KiB
 constexpr unsigned kLedgerSlotEmpty = 0xffffffffu;                 // (an id in the load table is below 2^32 - 1)
 
-struct alignas(16) LedgerI64x2 {
-  int64_t x, y;
-};
-struct alignas(8) LedgerI16x4 {
-  int16_t v[4];
-};
-
 __device__ __forceinline__ unsigned ledger_method_slot(unsigned m16) {
   return m16 < (unsigned)(kLedgerMethodSlots - 1) ? m16 : (unsigned)(kLedgerMethodSlots - 1);
 }
@@ -71,8 +64,8 @@ __device__ __forceinline__ void ledger_load4(const int* __restrict__ p, int64_t 
 }
 __device__ __forceinline__ void ledger_load4(const int64_t* __restrict__ p, int64_t i, int64_t M, int64_t (&o)[4]) {
   if (i + 4 <= M) {
-    const LedgerI64x2 lo = *reinterpret_cast<const LedgerI64x2*>(p + i);
-    const LedgerI64x2 hi = *reinterpret_cast<const LedgerI64x2*>(p + i + 2);
+    const I64x2 lo = *reinterpret_cast<const I64x2*>(p + i);
+    const I64x2 hi = *reinterpret_cast<const I64x2*>(p + i + 2);
     o[0] = lo.x, o[1] = lo.y, o[2] = hi.x, o[3] = hi.y;
     return;
   }
@@ -81,9 +74,8 @@ __device__ __forceinline__ void ledger_load4(const int64_t* __restrict__ p, int6
 }
 __device__ __forceinline__ void ledger_load4(const int16_t* __restrict__ p, int64_t i, int64_t M, int16_t (&o)[4]) {
   if (i + 4 <= M) {
-    const LedgerI16x4 v = *reinterpret_cast<const LedgerI16x4*>(p + i);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = v.v[c];
+    const I16x4 v = *reinterpret_cast<const I16x4*>(p + i);
+    o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
     return;
   }
 #pragma unroll

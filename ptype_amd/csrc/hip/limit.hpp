@@ -52,9 +52,7 @@ __host__ __device__ __forceinline__ uint32_t limit_busy_rows(int64_t M) {
 // hot slots one Send may have: their bins are indexed by an int (slot << kLimitDigit | digit)
 constexpr int64_t kLimitMaxHot = (1ll << 31 >> kLimitDigit) - 1;
 
-// What the admit pass leaves in st[i] for a row that travels: the marker shared with the
-// breaker and the reply cache (breaker.hpp kBreakerPending), selected by retry_select's raw mask.
-constexpr int kLimitPending = 31;
+constexpr int kLimitPending = kPending;  // what the admit pass leaves in st[i] for a row that travels
 
 enum LimitCounter {
   kLimitThrottled = 0,  // rows answered kStatusThrottled, cumulative

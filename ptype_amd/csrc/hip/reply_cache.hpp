@@ -27,10 +27,7 @@ static_assert(sizeof(ReplyCacheEntry) == 64, "ReplyCacheEntry must be one 64-B l
 constexpr int kReplyCacheMinLog2 = 4;
 constexpr int kReplyCacheMaxLog2 = 26;
 
-// What the lookup leaves in st[i] for a miss and for every non-pure message: a status no
-// handler returns, selected by retry_select's raw mask and replaced by the inner Send's
-// reply before the caller sees the outputs.
-constexpr int kReplyCachePending = 31;
+constexpr int kReplyCachePending = kPending;  // what the lookup leaves in st[i] for a miss and a non-pure message
 
 __host__ __device__ __forceinline__ uint64_t reply_cache_k0(uint32_t actor, uint32_t method16) {
   return (uint64_t)actor | (uint64_t)(method16 & 0xffffu) << 32;

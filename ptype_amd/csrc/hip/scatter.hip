@@ -45,13 +45,6 @@ constexpr int kScatterTile = kScatterThreads * kScatterQuads * 4;  // 2048 rows
 constexpr int kScatterSegs = kScatterQuads * kScatterWaves;        // 256-row segments of a tile
 constexpr int kScatterScanPer = 4;                                 // tile sums per thread and chunk of the scan
 
-struct alignas(16) ScatterI64x2 {
-  int64_t x, y;
-};
-struct alignas(8) ScatterI16x4 {
-  int16_t x, y, z, w;
-};
-
 struct ScatterRule {
   // ranges
   uint64_t step;
@@ -338,18 +331,18 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
     if (p + 4 <= rows) {
       *reinterpret_cast<int4*>(out.actor + at) = make_int4(actor[0], actor[1], actor[2], actor[3]);
       *reinterpret_cast<int4*>(out.group + at) = make_int4(group[0], group[1], group[2], group[3]);
-      *reinterpret_cast<ScatterI64x2*>(out.a0 + at) = ScatterI64x2{a0[0], a0[1]};
-      *reinterpret_cast<ScatterI64x2*>(out.a0 + at + 2) = ScatterI64x2{a0[2], a0[3]};
+      *reinterpret_cast<I64x2*>(out.a0 + at) = I64x2{a0[0], a0[1]};
+      *reinterpret_cast<I64x2*>(out.a0 + at + 2) = I64x2{a0[2], a0[3]};
       if (out.a1) {
-        *reinterpret_cast<ScatterI64x2*>(out.a1 + at) = ScatterI64x2{a1[0], a1[1]};
-        *reinterpret_cast<ScatterI64x2*>(out.a1 + at + 2) = ScatterI64x2{a1[2], a1[3]};
+        *reinterpret_cast<I64x2*>(out.a1 + at) = I64x2{a1[0], a1[1]};
+        *reinterpret_cast<I64x2*>(out.a1 + at + 2) = I64x2{a1[2], a1[3]};
       }
       if (out.a2) {
-        *reinterpret_cast<ScatterI64x2*>(out.a2 + at) = ScatterI64x2{a2[0], a2[1]};
-        *reinterpret_cast<ScatterI64x2*>(out.a2 + at + 2) = ScatterI64x2{a2[2], a2[3]};
+        *reinterpret_cast<I64x2*>(out.a2 + at) = I64x2{a2[0], a2[1]};
+        *reinterpret_cast<I64x2*>(out.a2 + at + 2) = I64x2{a2[2], a2[3]};
       }
       if constexpr (MCOL)
-        *reinterpret_cast<ScatterI16x4*>(out.method + at) = ScatterI16x4{method[0], method[1], method[2], method[3]};
+        *reinterpret_cast<I16x4*>(out.method + at) = I16x4{method[0], method[1], method[2], method[3]};
     } else {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {

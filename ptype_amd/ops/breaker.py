@@ -43,9 +43,8 @@ import torch
 from . import _ptr, hip, raw_stream
 from . import retry as RT
 from .batch import MsgBatch
-from .records import STATUS_BREAKER_OPEN, STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NOT_DELIVERED, STATUS_OK
+from .records import PENDING, STATUS_BREAKER_OPEN, STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NOT_DELIVERED, STATUS_OK
 
-PENDING = 31                 # breaker.hpp kBreakerPending
 MAX_TICK = 2**31 - 1         # breaker.hpp kBreakerMaxTick
 MAX_ACTORS = 1 << 28         # breaker.hpp kBreakerMaxActors
 DEFAULT_TRIP_ON = (STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NOT_DELIVERED)
@@ -241,21 +240,14 @@ class BreakerRef:
                 self.observe(batch, out[1])
                 return out
             val, st = self.admit(batch)
-            sub, idx, K = RT.select_mask(batch, st, 1 << PENDING)
-            c["rejected"] += M - K
-            c["sent"] += K
-            if K == 0 and not collective:
-                return val, st
-            if K == M:  # nothing rejected: the batch as it is, its result unchanged
-                out = send(batch)
-                self.observe(batch, out[1])
-                return out
-            out = send(sub)
-            self.observe(sub, out[1])
-            RT.merge(val, st, idx, out[0], out[1])
-            return (val, st) + tuple(out[2:])
+            return RT.send_pending(batch, val, st, send, collective, self._count,
+                                   lambda sub, out: self.observe(sub, out[1]))
         finally:
             self.end()
+
+    def _count(self, rejected: int, sent: int) -> None:
+        self.counters["rejected"] += rejected
+        self.counters["sent"] += sent
 
 
 class Breaker(BreakerRef):

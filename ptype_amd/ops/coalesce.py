@@ -29,6 +29,7 @@ import torch
 from . import _ptr, hip, raw_stream
 from .batch import MsgBatch
 from .records import PURE_METHODS
+from .retry import _aligned, _cols, _compact
 from .table import mix64
 
 MIN_LOG2, MAX_LOG2 = 4, 31  # coalesce.hpp kCoalesceMinLog2 / kCoalesceMaxLog2
@@ -124,20 +125,6 @@ class Coalescer:
         return self.table
 
 
-def _cols(batch: MsgBatch):
-    if batch.actor.dtype != torch.int32 or batch.a0.dtype != torch.int64:
-        raise TypeError("MsgBatch: actor must be int32 and a0..a2 int64")
-    for t in (batch.a0, batch.a1, batch.a2):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != batch.M):
-            raise TypeError("MsgBatch: actor must be int32 and a0..a2 int64")
-    c = (lambda t: None if t is None else t.contiguous())  # (a view at an odd offset stays naturally aligned)
-    uniform = isinstance(batch.method, int)
-    if not uniform and batch.method.numel() != batch.M:
-        raise TypeError("MsgBatch: the method column must have M entries")
-    method = None if uniform else batch.method.to(torch.int16).contiguous()
-    return c(batch.actor), c(batch.a0), c(batch.a1), c(batch.a2), method, uniform
-
-
 def group(batch: MsgBatch, coalescer: Coalescer | None = None, table_log2: int | None = None) -> torch.Tensor:
     """``lead int32[M]``: for a pure message the lowest ``j`` whose key equals message
     ``i``'s, ``i`` for any other.  ``table_log2`` forces the table's size (at least
@@ -159,11 +146,6 @@ def group(batch: MsgBatch, coalescer: Coalescer | None = None, table_log2: int |
     return lead
 
 
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    t = t.contiguous()  # the kernels read 16 bytes at a time (a view at an odd offset: copy)
-    return t.clone() if t.data_ptr() % 16 else t
-
-
 def select(batch: MsgBatch, lead: torch.Tensor):
     """The leaders of ``batch`` (``lead[i] == i``): ``(sub, idx, pos, K)`` with ``idx``
     int32[K] ascending, ``sub`` the K gathered rows of every column and ``pos``
@@ -172,32 +154,13 @@ def select(batch: MsgBatch, lead: torch.Tensor):
     M = batch.M
     if lead.dtype != torch.int32 or lead.numel() != M:
         raise TypeError("select: lead must be int32[M]")
-    dev = lead.device
-    uniform = isinstance(batch.method, int)
-    if dev.type != "cuda":
+    if lead.device.type != "cuda":
         idx = torch.nonzero(lead.to(torch.int64) == torch.arange(M)).flatten()
         K = int(idx.numel())
         pos = torch.full((M,), -1, dtype=torch.int32)
         pos[idx] = torch.arange(K, dtype=torch.int32)
         return batch.index_select(idx), idx.to(torch.int32), pos, K
-    actor, a0, a1, a2, method, _ = _cols(batch)
-    pos = torch.empty(M, dtype=torch.int32, device=dev)
-    if M == 0:
-        return batch, torch.empty(0, dtype=torch.int32, device=dev), pos, 0
-    lead = _aligned(lead)
-    new = (lambda t: None if t is None else torch.empty(M, dtype=t.dtype, device=dev))
-    idx = torch.empty(M, dtype=torch.int32, device=dev)
-    o_actor, o_a0, o_a1, o_a2, o_m = new(actor), new(a0), new(a1), new(a2), new(method)
-    h = hip()
-    T = int(h.coalesce_select_tile())
-    counts = torch.empty((M + T - 1) // T, dtype=torch.int32, device=dev)
-    k = torch.empty(1, dtype=torch.int32, device=dev)
-    h.coalesce_select(_ptr(lead), M, _ptr(actor), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(method), _ptr(idx), _ptr(pos),
-                      _ptr(o_actor), _ptr(o_a0), _ptr(o_a1), _ptr(o_a2), _ptr(o_m), _ptr(counts), _ptr(k),
-                      raw_stream(dev))
-    K = int(k.item())  # the one host read
-    n = (lambda t: None if t is None else t[:K])
-    return MsgBatch(o_actor[:K], o_a0[:K], n(o_a1), n(o_a2), batch.method if uniform else o_m[:K]), idx[:K], pos, K
+    return _compact(batch, lead, None)
 
 
 def fanout(lead: torch.Tensor, pos: torch.Tensor, v2: torch.Tensor, s2: torch.Tensor):

@@ -36,9 +36,8 @@ import torch
 from . import _ptr, hip, raw_stream
 from . import retry as RT
 from .batch import MsgBatch
-from .records import STATUS_THROTTLED
+from .records import PENDING, STATUS_THROTTLED
 
-PENDING = 31                 # limit.hpp kLimitPending (the breaker's and the reply cache's marker)
 MAX_TICK = 2**31 - 1         # limit.hpp kLimitMaxTick
 MAX_ACTORS = 1 << 28         # limit.hpp kLimitMaxActors
 DIGIT = 4                    # limit.hpp kLimitDigit
@@ -184,17 +183,14 @@ class LimiterRef:
             if cut is None:
                 c["sent"] += M
                 return send(batch)
-            val, st = cut
-            sub, idx, K = RT.select_mask(batch, st, 1 << PENDING)
-            c["rejected"] += M - K
-            c["sent"] += K
-            if K == 0 and not collective:
-                return val, st
-            out = send(sub)
-            RT.merge(val, st, idx, out[0], out[1])
-            return (val, st) + tuple(out[2:])
+            # (an actor is over its quota, so a row is rejected: the driver's K == M case never runs here)
+            return RT.send_pending(batch, cut[0], cut[1], send, collective, self._count)
         finally:
             self.end()
+
+    def _count(self, rejected: int, sent: int) -> None:
+        self.counters["rejected"] += rejected
+        self.counters["sent"] += sent
 
 
 class Limiter(LimiterRef):

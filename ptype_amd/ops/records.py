@@ -43,6 +43,9 @@ STATUS_NOT_DELIVERED = 5
 STATUS_RANK_LOST = 6  # the actor's rank died with the message in flight (re-homed since: re-send)
 STATUS_BREAKER_OPEN = 7  # not sent: the actor's circuit breaker is open (ops/breaker.py)
 STATUS_THROTTLED = 8  # not sent: the actor's token bucket is empty (ops/limit.py)
+# common.hpp kPending: what a Send wrapper (reply cache, breaker, limiter) leaves in st[i] for a
+# row that still has to travel -- a status no handler returns (retry.send_pending)
+PENDING = 31
 
 # names for people (Stats(), the Send ledger): the net/rpc service methods the ids stand for
 METHOD_NAMES = {

@@ -42,12 +42,12 @@ import torch
 from . import _ptr, hip, raw_stream
 from . import retry as RT
 from .batch import MsgBatch
-from .coalesce import _cols, _key_columns, key_hash
-from .records import PURE_METHODS, STATUS_OK
+from .coalesce import _key_columns, key_hash
+from .records import PENDING, PURE_METHODS, STATUS_OK
+from .retry import _cols
 
 MIN_LOG2, MAX_LOG2 = 4, 26  # reply_cache.hpp kReplyCacheMinLog2 / kReplyCacheMaxLog2
 DEFAULT_ENTRIES = 1 << 20   # 64 MiB
-PENDING = 31                # reply_cache.hpp kReplyCachePending
 WORDS = 8                   # uint64 words per entry
 W_K0, W_A0, W_A1, W_A2, W_VALUE, W_CLAIM, W_EPOCH = range(7)
 _U32 = 0xFFFFFFFF
@@ -176,19 +176,12 @@ class ReplyCacheRef:
             c["sent"] += M
             return send(batch)
         val, st = self.lookup(batch)
-        sub, idx, K = RT.select_mask(batch, st, 1 << PENDING)
-        c["hits"] += M - K
-        c["sent"] += K
-        if K == 0 and not collective:
-            return val, st
-        if K == M:  # all misses: the batch as it is, its result unchanged
-            out = send(batch)
-            self.insert(batch, out[0], out[1])
-            return out
-        out = send(sub)
-        self.insert(sub, out[0], out[1])
-        RT.merge(val, st, idx, out[0], out[1])
-        return (val, st) + tuple(out[2:])
+        return RT.send_pending(batch, val, st, send, collective, self._count,
+                               lambda sub, out: self.insert(sub, out[0], out[1]))
+
+    def _count(self, hits: int, sent: int) -> None:
+        self.counters["hits"] += hits
+        self.counters["sent"] += sent
 
 
 class ReplyCache(ReplyCacheRef):

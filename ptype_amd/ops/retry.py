@@ -4,7 +4,7 @@ The reference client retries a failed call up to ``Retries`` times, each attempt
 on a re-selected connection (cluster/rpc.go:59-116, ``withRetry`` around
 ``c.conns.Get()``).  On the batch path the failed messages of a Send are picked
 out of the batch on the device (``select``: a stable compaction by status, see
-``csrc/hip/retry.hip``), sent again as a sub-batch, and their replies put back
+``csrc/hip/compact.hpp``), sent again as a sub-batch, and their replies put back
 into the caller's outputs (``merge``).
 
 CUDA tensors run the kernels; the host learns K, the number of selected
@@ -18,7 +18,7 @@ import torch
 
 from . import _ptr, hip, raw_stream
 from .batch import MsgBatch
-from .records import (ORDERED_METHODS, STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NO_METHOD, STATUS_NOT_DELIVERED,
+from .records import (ORDERED_METHODS, PENDING, STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NO_METHOD, STATUS_NOT_DELIVERED,
                       STATUS_OVERFLOW, STATUS_RANK_LOST, method_ordered)
 
 RETRYABLE = frozenset({STATUS_FAILED, STATUS_NOT_DELIVERED, STATUS_NO_ACTOR, STATUS_NO_METHOD})
@@ -74,46 +74,92 @@ def select(batch: MsgBatch, status: torch.Tensor, retry_on=DEFAULT_RETRY_ON):
     return select_mask(batch, status, retry_mask(retry_on))
 
 
-def select_mask(batch: MsgBatch, status: torch.Tensor, mask: int):
-    """``select`` by a raw 32-bit mask (bit s set: status s is selected), unvalidated:
-    the reply cache compacts its misses by a marker status of its own
-    (ops/reply_cache.py)."""
+TILE = 4096  # rows per block of the compaction (compact.hpp kCompactTile, ``hip().retry_tile()``)
+
+
+def _cols(batch: MsgBatch):
     M = batch.M
-    if status.dtype != torch.int32 or status.numel() != M:
-        raise TypeError("select: status must be int32[M]")
-    dev = status.device
-    uniform = isinstance(batch.method, int)
-    if dev.type != "cuda":
-        idx = torch.nonzero(_selected(status, mask)).flatten()
-        return batch.index_select(idx), idx.to(torch.int32), int(idx.numel())
     if batch.actor.dtype != torch.int32 or batch.a0.dtype != torch.int64:
         raise TypeError("MsgBatch: actor must be int32 and a0..a2 int64")
-    if M == 0:
-        e = (lambda t: None if t is None else t[:0])
-        return (MsgBatch(batch.actor[:0], batch.a0[:0], e(batch.a1), e(batch.a2), batch.method if uniform
-                         else batch.method[:0]), torch.empty(0, dtype=torch.int32, device=dev), 0)
-    status = status.contiguous()
-    if status.data_ptr() % 16:  # (a view at an odd offset: the kernels read 16 bytes at a time)
-        status = status.clone()
-    c = (lambda t: None if t is None else t.contiguous())
-    actor, a0, a1, a2 = c(batch.actor), c(batch.a0), c(batch.a1), c(batch.a2)
-    for t in (a1, a2):
-        if t is not None and t.dtype != torch.int64:
+    for t in (batch.a0, batch.a1, batch.a2):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != M):
             raise TypeError("MsgBatch: actor must be int32 and a0..a2 int64")
+    c = (lambda t: None if t is None else t.contiguous())  # (a view at an odd offset stays naturally aligned)
+    uniform = isinstance(batch.method, int)
+    if not uniform and batch.method.numel() != M:
+        raise TypeError("MsgBatch: the method column must have M entries")
     method = None if uniform else batch.method.to(torch.int16).contiguous()
+    return c(batch.actor), c(batch.a0), c(batch.a1), c(batch.a2), method, uniform
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()  # the kernels read 16 bytes at a time (a view at an odd offset: copy)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _compact(batch: MsgBatch, key: torch.Tensor, mask: int | None):
+    """The stable compaction on a GPU (``csrc/hip/compact.hpp``): the rows of ``batch``
+    whose ``key`` (int32[M]) is a status in ``mask`` or, with ``mask`` None, the row's own
+    index.  ``(sub, idx, pos, K)``: ``sub`` and ``idx`` are views of M-row buffers, since K
+    is known only after the kernels ran; ``pos`` int32[M] (the row's place in ``sub``, or
+    -1) only without a mask, else None."""
+    M, dev = batch.M, key.device
+    actor, a0, a1, a2, method, uniform = _cols(batch)
     new = (lambda t: None if t is None else torch.empty(M, dtype=t.dtype, device=dev))
+    pos = torch.empty(M, dtype=torch.int32, device=dev) if mask is None else None
     idx = torch.empty(M, dtype=torch.int32, device=dev)
     o_actor, o_a0, o_a1, o_a2, o_m = new(actor), new(a0), new(a1), new(a2), new(method)
-    h = hip()
-    T = int(h.retry_tile())
-    counts = torch.empty((M + T - 1) // T, dtype=torch.int32, device=dev)
-    k = torch.empty(1, dtype=torch.int32, device=dev)
-    h.retry_select(_ptr(status), M, mask, _ptr(actor), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(method), _ptr(idx),
-                   _ptr(o_actor), _ptr(o_a0), _ptr(o_a1), _ptr(o_a2), _ptr(o_m), _ptr(counts), _ptr(k),
-                   raw_stream(dev))
-    K = int(k.item())  # the one host read
+    K = 0
+    if M:
+        key = _aligned(key)
+        counts = torch.empty((M + TILE - 1) // TILE, dtype=torch.int32, device=dev)
+        k = torch.empty(1, dtype=torch.int32, device=dev)
+        cols = (_ptr(actor), _ptr(a0), _ptr(a1), _ptr(a2), _ptr(method), _ptr(idx))
+        outs = (_ptr(o_actor), _ptr(o_a0), _ptr(o_a1), _ptr(o_a2), _ptr(o_m), _ptr(counts), _ptr(k), raw_stream(dev))
+        if mask is None:
+            hip().coalesce_select(_ptr(key), M, *cols, _ptr(pos), *outs)
+        else:
+            hip().retry_select(_ptr(key), M, mask, *cols, *outs)
+        K = int(k.item())  # the one host read
     n = (lambda t: None if t is None else t[:K])
-    return MsgBatch(o_actor[:K], o_a0[:K], n(o_a1), n(o_a2), batch.method if uniform else o_m[:K]), idx[:K], K
+    return MsgBatch(o_actor[:K], o_a0[:K], n(o_a1), n(o_a2), batch.method if uniform else o_m[:K]), idx[:K], pos, K
+
+
+def select_mask(batch: MsgBatch, status: torch.Tensor, mask: int):
+    """``select`` by a raw 32-bit mask (bit s set: status s is selected), unvalidated:
+    the Send wrappers compact their rows by a marker status of their own
+    (``send_pending``)."""
+    if status.dtype != torch.int32 or status.numel() != batch.M:
+        raise TypeError("select: status must be int32[M]")
+    if status.device.type != "cuda":
+        idx = torch.nonzero(_selected(status, mask)).flatten()
+        return batch.index_select(idx), idx.to(torch.int32), int(idx.numel())
+    sub, idx, _, K = _compact(batch, status, mask)
+    return sub, idx, K
+
+
+def send_pending(batch: MsgBatch, val: torch.Tensor, st: torch.Tensor, send, collective: bool, count, after=None):
+    """The Send of a wrapper that answered some rows itself (reply cache, breaker,
+    limiter): ``(val, st)`` are the batch's outputs so far, with ``st[i] == PENDING`` on
+    the rows that still travel.  Those are compacted (stably, in message order),
+    ``count(M - K, K)`` tells the wrapper how many were held back and how many go on,
+    then ``send(sub)`` -- it takes a MsgBatch and returns ``(value, status, ...)``, final
+    on return -- ``after(sub, out)``, and the replies are merged into ``(val, st)``.
+    ``send`` is called at most once: exactly once when ``collective`` (a rank with
+    nothing to send joins with an empty batch), not at all for K == 0 otherwise.  With
+    K == M the batch itself is sent, and ``send``'s result returned unchanged."""
+    M = batch.M
+    sub, idx, K = select_mask(batch, st, 1 << PENDING)
+    count(M - K, K)
+    if K == 0 and not collective:
+        return val, st
+    out = send(batch if K == M else sub)
+    if after is not None:
+        after(batch if K == M else sub, out)
+    if K == M:
+        return out
+    merge(val, st, idx, out[0], out[1])
+    return (val, st) + tuple(out[2:])
 
 
 def merge(val: torch.Tensor, st: torch.Tensor, idx: torch.Tensor, v2: torch.Tensor, s2: torch.Tensor) -> None:

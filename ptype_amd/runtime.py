@@ -515,18 +515,19 @@ class DeviceRuntime:
                              "gpu.ledger)")
         if (self._exchange is not None and self._exchange._capturing) or (
                 self.on_gpu and torch.cuda.is_current_stream_capturing()):
-            if coalesce:
-                raise ValueError("send(coalesce=True) inside a captured Send: selecting the leaders needs a host read")
-            if cache:
-                raise ValueError("send(cache=True) inside a captured Send: selecting the misses needs a host read")
-            if breaker:
-                raise ValueError("send(breaker=True) inside a captured Send: the count of open actors is read on the "
-                                 "host")
-            raise ValueError("send(limit=True) inside a captured Send: the count of actors over their quota is read on "
-                             "the host")
+            for on, name, why in ((coalesce, "coalesce", "selecting the leaders needs a host read"),
+                                  (cache, "cache", "selecting the misses needs a host read"),
+                                  (breaker, "breaker", "the count of open actors is read on the host"),
+                                  (limit, "limit", "the count of actors over their quota is read on the host")):
+                if on:
+                    raise ValueError(f"send({name}=True) inside a captured Send: {why}")
         ledger = self.ledger if account is None or account else None
         # the inner Send accounts nothing: the full batch is accounted below, on the replies it returns
         inner = (lambda sub: self._send(service, sub, resend_overflow, router, retries, retry_on, False, final=True))
+
+        def wrap(w, inner):
+            return lambda sub: w.send(sub, inner, collective=self.world > 1)
+
         if limit:
             if self._limiter is None:
                 from .ops.limit import Limiter
@@ -535,59 +536,54 @@ class DeviceRuntime:
                                         self.limit_burst)
             if router is None:
                 self._check_service(service)  # (an all-throttled Send never reaches _send's check)
-            unlimited = inner
-            inner = (lambda sub: self._limiter.send(sub, unlimited, collective=self.world > 1))
+            inner = wrap(self._limiter, inner)
         if breaker:
             if self._breaker is None:
                 from .ops.breaker import Breaker
 
                 self._breaker = Breaker(self.device, self.breaker_actors or self.total_actors, self.breaker_threshold,
                                         self.breaker_cooldown, self.breaker_trip_on)
-            self.sync()
-            if router is not None:
-                router.refresh()
-            else:
-                self._check_service(service)  # (an all-rejected Send never reaches _send's check)
-            seen = (self._registry_changes, router, None if router is None else router.changes)
-            last = self._breaker_seen
+            seen, last = self._existence_stamp(service, router), self._breaker_seen
             if last is not None and (seen[0] != last[0] or (seen[1] is last[1] and seen[2] != last[2])):
                 self._breaker.reset()
             self._breaker_seen = seen
-            unguarded = inner
-            inner = (lambda sub: self._breaker.send(sub, unguarded, collective=self.world > 1))
+            inner = wrap(self._breaker, inner)
         if cache:
             if self._cache is None:
                 from .ops.reply_cache import ReplyCache
 
                 self._cache = ReplyCache(self.device, self.cache_entries)
-            self.sync()
-            if router is not None:
-                router.refresh()
-            else:
-                self._check_service(service)  # (an all-hit Send never reaches _send's check)
-            # (the router itself is kept, not its id(): a collected router's id can be reused)
-            seen = (self._registry_changes, router, None if router is None else router.changes)
-            last = self._cache_seen
+            seen, last = self._existence_stamp(service, router), self._cache_seen
             if last is None or seen[0] != last[0] or seen[1] is not last[1] or seen[2] != last[2]:
                 if last is not None:
                     self._cache.clear()
                 self._cache_seen = seen
-            uncached = inner
-            inner = (lambda sub: self._cache.send(sub, uncached, collective=self.world > 1))
+            inner = wrap(self._cache, inner)
         if not coalesce:
-            out = inner(batch)
-            if ledger is not None:
-                ledger.account(batch, out[0], out[1])
-            if gather is not None:
-                gather.reduce(out[0], out[1])
-            return out
+            return self._settle(batch, inner(batch), ledger, gather)
         if self._coalescer is None:
             from .ops.coalesce import Coalescer
 
             self._coalescer = Coalescer(self.device, self.max_batch)
-        out, _ = self._coalescer.send(batch, inner)
+        return self._settle(batch, self._coalescer.send(batch, inner)[0], ledger, gather)
+
+    def _existence_stamp(self, service: str | None, router):
+        """What decides whether an actor exists, brought up to date: the registry change
+        counter, the router (itself, not its id(): a collected router's id can be reused)
+        and its record counter.  A Send whose wrappers answer every row never reaches
+        ``_send``'s service check, so it is made here."""
+        self.sync()
+        if router is not None:
+            router.refresh()
+        else:
+            self._check_service(service)
+        return self._registry_changes, router, None if router is None else router.changes
+
+    def _settle(self, batch: B.MsgBatch, out, ledger, gather, logical=None):
+        """A Send's final replies into the ledger (``batch`` under its ``logical`` actor
+        ids, when a router rewrote them) and the gather; returns ``out``."""
         if ledger is not None:
-            ledger.account(batch, out[0], out[1])
+            ledger.account(batch if logical is None else self._logical_batch(batch, logical), out[0], out[1])
         if gather is not None:
             gather.reduce(out[0], out[1])
         return out
@@ -692,12 +688,7 @@ class DeviceRuntime:
             if ledger is not None or gather is not None:  # on its final replies: never deferred
                 if resend_overflow:
                     return ex.send_all(batch, logical=logical, ledger=ledger, gather=gather, **rkw)
-                out = ex.send(batch)
-                if ledger is not None:
-                    ledger.account(self._logical_batch(batch, logical), out[0], out[1])
-                if gather is not None:
-                    gather.reduce(out[0], out[1])
-                return out
+                return self._settle(batch, ex.send(batch), ledger, gather, logical)
             # more than one rank: no host wait on this Send (its overflow, if any, is
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
             if rkw:
@@ -758,20 +749,13 @@ class DeviceRuntime:
                         raise
                     self.recover()  # the batch WAS delivered: recover, never re-send it
             if todo is None:
-                if ledger is not None:
-                    ledger.account(self._logical_batch(batch, logical), out[0], out[1])
-                if gather is not None:
-                    gather.reduce(out[0], out[1])
-                return out
+                return self._settle(batch, out, ledger, gather, logical)
             val = torch.zeros(batch.M, dtype=out[0].dtype, device=out[0].device)
             st = torch.full((batch.M,), STATUS_RANK_LOST, dtype=out[1].dtype, device=out[1].device)
             val[todo] = out[0]
             st[todo] = out[1]
-            if ledger is not None:  # the whole batch, the STATUS_RANK_LOST rows included
-                ledger.account(self._logical_batch(batch, logical), val, st)
-            if gather is not None:
-                gather.reduce(val, st)
-            return (val, st) + tuple(out[2:])
+            # the whole batch, the STATUS_RANK_LOST rows included
+            return self._settle(batch, (val, st) + tuple(out[2:]), ledger, gather, logical)
         raise AssertionError("unreachable")
 
     @staticmethod

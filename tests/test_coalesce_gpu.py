@@ -185,6 +185,53 @@ def test_unaligned_column_views():
     assert torch.equal(val.cpu(), j + 1) and torch.equal(st.cpu(), (j + 1).to(torch.int32))
 
 
+TS = 4096  # rows per block of the selection (the retry path's tile, checked below)
+
+LEADS = {
+    "all": lambda M: torch.arange(M, dtype=torch.int32),
+    "row0": lambda M: torch.zeros(M, dtype=torch.int32),
+    "every7": lambda M: (torch.arange(M) - torch.arange(M) % 7).to(torch.int32),
+    "last": lambda M: torch.cat([torch.zeros(max(M - 1, 0), dtype=torch.int32),
+                                 torch.full((min(M, 1),), M - 1, dtype=torch.int32)]),
+}
+
+
+def _select_alone(M):
+    """``CO.select`` of hand-made ``lead`` columns on the GPU against its CPU path: idx,
+    pos, K and every gathered column, exactly (no grouping kernel runs)."""
+    i = torch.arange(M, dtype=torch.int64)
+    b = MsgBatch(i.to(torch.int32) * 5 - 7, i * 3 - 2**40, None, i * i + 1, (i % 251).to(torch.int16))
+    bg = _cuda(b)
+    for name, make in LEADS.items():
+        lead = make(M)
+        assert lead.numel() == M and bool((lead.to(torch.int64) <= i).all())
+        assert torch.equal(lead[lead.to(torch.int64)], lead)  # a leader leads itself
+        rsub, ridx, rpos, rK = CO.select(b, lead)
+        leads = [lead.cuda()]
+        if name == "every7":  # and as a view 4 bytes past a 16-byte boundary
+            leads.append(torch.cat([torch.zeros(1, dtype=torch.int32), lead]).cuda()[1:])
+            assert M == 0 or leads[1].data_ptr() % 16 == 4
+        for gl in leads:
+            sub, idx, pos, K = CO.select(bg, gl)
+            assert K == rK and idx.dtype == torch.int32 and torch.equal(idx.cpu(), ridx), (M, name)
+            assert pos.dtype == torch.int32 and torch.equal(pos.cpu(), rpos), (M, name)
+            assert torch.equal(sub.actor.cpu(), rsub.actor) and torch.equal(sub.a0.cpu(), rsub.a0), (M, name)
+            assert sub.a1 is None and rsub.a1 is None and torch.equal(sub.a2.cpu(), rsub.a2), (M, name)
+            assert sub.method.dtype == torch.int16 and torch.equal(sub.method.cpu(), rsub.method), (M, name)
+
+
+@pytest.mark.parametrize("M", [0, 1, 63, 64, 65, TS - 1, TS, TS + 1, 3 * TS + 17])
+def test_select_alone_at_its_own_tile(M):
+    assert hip().retry_tile() == TS
+    _select_alone(M)
+
+
+def test_select_alone_more_tiles_than_summing_threads():
+    """257 tiles + a partial one: the block that sums the tile counts below it (256
+    threads) takes more than one value per thread."""
+    _select_alone(257 * TS + 5)
+
+
 @pytest.mark.parametrize("M", [1, 63, 65, T + 1, 3 * T + 17])
 def test_fanout_against_torch_indexing(M):
     for seed, kw in enumerate(({}, {"methods": METHOD_ECHO, "span": 2, "actors": 1}, {"span": 1000, "actors": 1000})):

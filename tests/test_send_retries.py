@@ -15,7 +15,7 @@ from ptype_amd.ops import retry as R
 from ptype_amd.ops.batch import MsgBatch
 from ptype_amd.ops.records import (METHOD_CALC_MULTIPLY, METHOD_COUNTER_ADD, METHOD_RETRY_TEST, METHOD_SEQ_FOLD,
                                    STATUS_FAILED, STATUS_NO_ACTOR, STATUS_NO_METHOD, STATUS_NOT_DELIVERED, STATUS_OK,
-                                   STATUS_OVERFLOW, STATUS_RANK_LOST)
+                                   STATUS_OVERFLOW, STATUS_RANK_LOST, STATUS_THROTTLED)
 from ptype_amd.ops.table import RegistryTable, actor_keys
 from ptype_amd.parallel.exchange import ActorExchange
 
@@ -81,6 +81,59 @@ def test_select_reference_and_merge():
     ev[want], es[want] = v2, s2
     R.merge(val, st, want.to(torch.int32), v2, s2)
     assert torch.equal(val, ev) and torch.equal(st, es)
+
+
+def test_send_pending_driver():
+    """The sub-batch driver of the reply cache, the breaker and the limiter
+    (``send_pending``) with a fake ``send``: how often it is called and with what,
+    what ``after`` sees, the counts reported before the Send, and the merge."""
+    M = 10
+    b = MsgBatch(torch.arange(M, dtype=torch.int32), torch.arange(M, dtype=torch.int64) * 3, None, None,
+                 METHOD_RETRY_TEST)
+    log = []
+
+    def send(sub):
+        log.append(("send", sub))
+        return sub.a0 + 100, torch.full((sub.M,), STATUS_FAILED, dtype=torch.int32), "extra", 7
+
+    count = (lambda held, sent: log.append(("count", held, sent)))
+    after = (lambda sub, out: log.append(("after", sub, out)))
+    outputs = (lambda st: (-torch.arange(M, dtype=torch.int64), torch.tensor(st, dtype=torch.int32)))
+
+    # K == 0, not collective: the outputs as they are, no call
+    val, st = outputs([STATUS_OK] * M)
+    out = R.send_pending(b, val, st, send, False, count, after)
+    assert out[0] is val and out[1] is st and len(out) == 2 and log == [("count", M, 0)]
+    # K == 0, collective: one call with an empty batch; nothing is merged
+    del log[:]
+    out = R.send_pending(b, val, st, send, True, count, after)
+    assert [e[0] for e in log] == ["count", "send", "after"] and log[0] == ("count", M, 0)
+    assert log[1][1].M == 0 and log[2][1] is log[1][1]
+    assert out[0] is val and out[1] is st and out[2:] == ("extra", 7)
+    assert torch.equal(val, -torch.arange(M)) and st.tolist() == [STATUS_OK] * M
+    # K == M: the batch itself goes out, send's result comes back as it is, after sees the batch
+    del log[:]
+    val, st = outputs([R.PENDING] * M)
+    out = R.send_pending(b, val, st, send, False, count, after)
+    assert [e[0] for e in log] == ["count", "send", "after"] and log[0] == ("count", 0, M)
+    assert log[1][1] is b and log[2][1] is b and log[2][2] is out and out[2:] == ("extra", 7)
+    assert torch.equal(out[0], b.a0 + 100) and out[0] is not val
+    # 0 < K < M: after sees the sub-batch, the replies are merged into the rows that travelled
+    del log[:]
+    val, st = outputs([R.PENDING if i % 3 == 1 else STATUS_THROTTLED for i in range(M)])
+    out = R.send_pending(b, val, st, send, False, count, after)
+    went = [1, 4, 7]
+    assert [e[0] for e in log] == ["count", "send", "after"] and log[0] == ("count", M - 3, 3)
+    sub = log[1][1]
+    assert sub is log[2][1] and sub.actor.tolist() == went and sub.a0.tolist() == [3, 12, 21]
+    assert sub.method == METHOD_RETRY_TEST and torch.equal(log[2][2][0], sub.a0 + 100)
+    assert out[0] is val and out[1] is st and out[2:] == ("extra", 7)
+    assert val.tolist() == [3 * i + 100 if i in went else -i for i in range(M)]
+    assert st.tolist() == [STATUS_FAILED if i in went else STATUS_THROTTLED for i in range(M)]
+    # without an after hook
+    del log[:]
+    R.send_pending(b, *outputs([R.PENDING] * M), send, False, count)
+    assert [e[0] for e in log] == ["count", "send"]
 
 
 def test_retry_on_validation():

@@ -68,7 +68,7 @@ def _check_select(b, status, retry_on):
 
 @pytest.mark.parametrize("M", [0, 1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 17])
 def test_retry_select_sizes_and_patterns(M):
-    assert hip().retry_tile() == T
+    assert hip().retry_tile() == T == R.TILE
     b = _batch(M, True, True, True)
     for i, p in enumerate(PATTERNS):
         _check_select(b, _status(M, p, seed=i), (STATUS_FAILED,))
