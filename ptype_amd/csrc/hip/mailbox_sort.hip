@@ -327,10 +327,13 @@ __host__ __device__ constexpr size_t persist_lds_bytes(uint32_t S) {
   return (size_t)S * (8 + 4 + 2 * 4 + 2 * 4 * (kST / kWave));
 }
 
+// (amdgpu_waves_per_eu: with the lean store loop beside the general one the register allocator, left
+// to itself, settles at 137 VGPRs and three waves per SIMD; told the occupancy the kernel is built
+// around it fits 128 without scratch)
 template <int = 0>
-__global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx,
-                                                               uint32_t* __restrict__ tinfo, uint32_t* __restrict__ rw,
-                                                               ReplyView rv) {
+__global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx, uint32_t* __restrict__ tinfo,
+                             uint32_t* __restrict__ rw, ReplyView rv) {
   constexpr int SK = kSK;
   extern __shared__ __align__(16) unsigned char smem_ps[];
   const uint32_t S = 1u << mv.log_s;
@@ -341,6 +344,7 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
   uint32_t* lpres = reinterpret_cast<uint32_t*>(smem_ps + ((persist_lds_bytes(S) + 15) & ~(size_t)15));
   __shared__ uint32_t tmax[3];
   __shared__ uint32_t vote[2];  // the spill vote's flag word of a tile, double-buffered like pre / wcnt
+  __shared__ uint32_t brot[kStatelessShards];  // (lean) each ring's tail + rotation, low word
   const unsigned w = threadIdx.x / kWave, lane = lane_id();
   // this block's tiles: first, first + stride, ... (n of them)
   const uint32_t G = gridDim.x, T = in.tiles;
@@ -358,6 +362,7 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
     uint64_t tl;
     room[s] = os_ring_room(mv, s, tl);
     base[s] = tl;
+    if (s < kStatelessShards) brot[s] = (uint32_t)tl + shard_rot(mv, s);
   }
   if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
   if (threadIdx.x < 2) vote[threadIdx.x] = 0;
@@ -365,6 +370,10 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
   __syncthreads();
   const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
   const bool maxima = in.rec8 || in.recw;
+  // the lean store loop (os_store_lean) serves the 8-B stateless Send on its own rings' runs; a tile
+  // that spilled keeps os_store_msg
+  const bool lean = in.rec8 && !in.recw && tinfo != nullptr && rv.slots == nullptr && S <= kStatelessShards &&
+                    rings_small(mv);
   uint32_t n_enq = 0, n_ovf = 0, n_miss = 0, n_spill = 0;  // (a block's share of a batch: below 2^32)
   // the first tile, up to its reservations in flight; its arguments behind its actors
   uint32_t nx[SK];  // the coming tile: actors, then mailboxes
@@ -411,7 +420,7 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
       pre[s] = rx;
       sp = os_run_info(mv, tinfo, t, S, s, base[s], room[s], rx, rc);
     }
-    const uint32_t escm = os_fields<SK>(in, w8, mb, v0, v1, tmax);
+    const uint32_t escm = os_fields<SK, true>(in, w8, mb, v0, v1, tmax);
     sp |= escm != 0;
     // the spill vote: a wave with a spilling lane sets this tile's flag word, read behind the tile's barrier
     if (__any(sp) && lane == 0) vote[b] = 1u;
@@ -425,12 +434,39 @@ __global__ __launch_bounds__(kST) void mbx_persist_sort_kernel(SortIn in, MboxVi
         tmax[0] = tmax[1] = tmax[2] = 0;
       }
     }
+    if (lean && !tile_spill) {
+      // every run fits its room and every field its width: this wave's ring positions per shard, once
+      // (its own row of the wave offsets, not read again before the tile after the next clears it), and
+      // the enqueued count from the runs' counts
+      uint32_t* wpos = wcnt_all + w * S;
+      if (lane < S) wpos[lane] += pre[lane] + brot[lane];
+      __builtin_amdgcn_wave_barrier();  // (one wave: its LDS accesses are in order)
+      if (threadIdx.x < S) n_enq += rc;
+      const Rec8Fast f8 = rec8_fast(w8);
+      const uint32_t place0 = w * (SK * kWave) + lane;  // this thread's first place in a tile
+      if (f8.ok) {
 #pragma unroll
-    for (int k = 0; k < SK; ++k) {
-      const int64_t i = tile_index<SK>(t, k);
-      if (!full && i >= in.M) continue;
-      os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], 0, in.method_uniform,
-                       (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
+        for (int k = 0; k < SK; ++k) {
+          const int64_t i = tile_index<SK>(t, k);
+          if (!full && i >= in.M) continue;
+          os_store_lean<SK, true>(in, mv, rv, i, place0 + k * kWave, wpos, mb[k], wrp[k], v0[k], v1[k], f8, w8, n_miss);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < SK; ++k) {
+          const int64_t i = tile_index<SK>(t, k);
+          if (!full && i >= in.M) continue;
+          os_store_lean<SK, false>(in, mv, rv, i, place0 + k * kWave, wpos, mb[k], wrp[k], v0[k], v1[k], f8, w8, n_miss);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < SK; ++k) {
+        const int64_t i = tile_index<SK>(t, k);
+        if (!full && i >= in.M) continue;
+        os_store_msg<SK>(in, mv, rv, i, base, room, pre, wcnt_all + w * S, mb[k], wrp[k], v0[k], v1[k], 0, in.method_uniform,
+                         (escm >> k) & 1u, w8, true, tile_spill, sidx, rw, n_enq, n_ovf, n_miss, n_spill);
+      }
     }
     if (more) {
       // the next tile's arguments, right behind this tile's stores: in flight across its resolve, rank,

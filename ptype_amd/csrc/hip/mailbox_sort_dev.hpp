@@ -248,7 +248,7 @@ __device__ __forceinline__ int os_run_info(const MboxView& mv, uint32_t* __restr
 // (in.rec8 / in.recw) the tile's fields OR-ed, their bit lengths max-ed into `tmax` (LDS,
 // read past the next barrier); returns the mask of this thread's messages whose fields do
 // not fit an 8-B record of widths `w8`.
-template <int SK>
+template <int SK, bool OR_FIRST = false>
 __device__ __forceinline__ uint32_t os_fields(const SortIn& in, uint32_t w8, const uint32_t (&mb)[SK],
                                               const int64_t (&v0)[SK], const int64_t (&v1)[SK], uint32_t* tmax) {
   uint32_t escm = 0;
@@ -261,7 +261,19 @@ __device__ __forceinline__ uint32_t os_fields(const SortIn& in, uint32_t w8, con
     const uint64_t z0 = ((uint64_t)v0[k] << 1) ^ (uint64_t)(v0[k] >> 63);
     const uint64_t z1 = ((uint64_t)v1[k] << 1) ^ (uint64_t)(v1[k] >> 63);
     or_m |= mb[k], or_0 |= z0, or_1 |= z1;
-    if (in.rec8 && ((mb[k] >> wm) != 0 || (z0 >> w0) != 0 || (z1 >> w1) != 0)) escm |= 1u << k;
+    if constexpr (!OR_FIRST)
+      if (in.rec8 && ((mb[k] >> wm) != 0 || (z0 >> w0) != 0 || (z1 >> w1) != 0)) escm |= 1u << k;
+  }
+  // OR_FIRST (the persistent sort): the thread's OR-ed fields tested first, and only a thread whose
+  // OR does not fit looks for the items (the per-item tests cost the one-block-per-tile kernels a VGPR less)
+  if (OR_FIRST && in.rec8 && ((or_m >> wm) | (or_0 >> w0) | (or_1 >> w1)) != 0) {
+#pragma unroll
+    for (int k = 0; k < SK; ++k) {
+      if (mb[k] == kNoSlot) continue;
+      const uint64_t z0 = ((uint64_t)v0[k] << 1) ^ (uint64_t)(v0[k] >> 63);
+      const uint64_t z1 = ((uint64_t)v1[k] << 1) ^ (uint64_t)(v1[k] >> 63);
+      if ((mb[k] >> wm) != 0 || (z0 >> w0) != 0 || (z1 >> w1) != 0) escm |= 1u << k;
+    }
   }
   const uint32_t bm = wave_max_u32(bitlen64(or_m)), b0 = wave_max_u32(bitlen64(or_0)),
                  b1 = wave_max_u32(bitlen64(or_1));
@@ -289,6 +301,78 @@ struct PackedRanks {
   uint32_t p[SK / 2];
   __device__ __forceinline__ uint32_t operator[](int k) const { return (p[k >> 1] >> ((k & 1) * 16)) & 0xffffu; }
 };
+
+// ---- the lean bodies of the 8-B stateless Send (profiles/lean_bodies.md): what the persistent
+// sort's store loop and the narrow ring drain run per record when nothing of the general case
+// can occur, chosen by block-uniform tests.
+//
+// Rings whose every 8-B cell lies within 4 GB of plane A's start: a slot's byte offset fits
+// 32 bits, so a record's address is a scalar base plus a 32-bit offset.
+__device__ __forceinline__ bool rings_small(const MboxView& mv) { return mv.log_s + mv.log_q <= 29; }
+
+// 8-B field widths that pack and decode in 32-bit operations: the place and the mailbox lie in
+// the low word (12 + wm < 32), a0's field straddles or ends at the words' boundary, a1's lies
+// in the high word, and both arguments' zigzags fit 32 bits.
+struct Rec8Fast {
+  uint32_t s0;   // a0's field starts here (13..31)
+  uint32_t s1h;  // a1's field starts here in the high word (0..31)
+  uint32_t m0;   // a0's field mask
+  uint32_t mm;   // the mailbox's field mask
+  bool ok;
+};
+__device__ __forceinline__ Rec8Fast rec8_fast(uint32_t w8) {
+  const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu, w1 = (w8 >> 16) & 0xffu;
+  Rec8Fast f;
+  f.s0 = 12 + wm;
+  f.ok = f.s0 < 32 && w0 >= 1 && w0 <= 32 && w1 <= 32 && f.s0 + w0 >= 32 && f.s0 + w0 < 64;
+  f.s1h = (f.s0 + w0) & 31u;
+  f.m0 = w0 >= 32 ? 0xffffffffu : (1u << (w0 & 31u)) - 1u;
+  f.mm = (1u << (wm & 31u)) - 1u;
+  return f;
+}
+// (x fits its field: it is an int32, and its zigzag a u32)
+__device__ __forceinline__ uint32_t zigzag32(int64_t x) {
+  const uint32_t lo = (uint32_t)x;
+  return (lo << 1) ^ (uint32_t)((int32_t)lo >> 31);
+}
+__device__ __forceinline__ uint64_t pack_rec8_fast(const Rec8Fast& f, uint32_t place, uint32_t mb, int64_t x0, int64_t x1) {
+  const uint32_t z0 = zigzag32(x0), z1 = zigzag32(x1);
+  const uint32_t lo = place | (mb << 12) | (z0 << f.s0);
+  const uint32_t hi = (z0 >> (32u - f.s0)) | (z1 << f.s1h);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The lean store of one message of a tile that did not spill (no run past its room, no field
+// past its width): `wpos` is this wave's row of ring positions -- the low word of tail +
+// rotation + the tile's prefix + the wave's offset, per shard (built behind the tile's
+// barrier) -- so a record's slot is one LDS read, an add, a mask and a shift-or in 32 bits.
+// rv.slots is null (the caller's test): a miss's status is a plain store.
+template <int SK, bool FAST>
+__device__ __forceinline__ void os_store_lean(const SortIn& in, const MboxView& mv, const ReplyView& rv, int64_t i,
+                                              uint32_t place, const uint32_t* wpos, uint32_t mbk, uint32_t wrk,
+                                              int64_t x0, int64_t x1, const Rec8Fast& f, uint32_t w8, uint32_t& n_miss) {
+  if (mbk == kNoSlot) {
+    ++n_miss;
+    const uint32_t origin = in.origin_base + (uint32_t)i;
+    if ((uint64_t)origin < rv.n) {
+      rv.val[origin] = 0;
+      rv.st[origin] = kStatusNoActor;
+    }
+    return;
+  }
+  const uint32_t sh = mbk & ((1u << mv.log_s) - 1u);
+  const uint32_t slot = (sh << mv.log_q) | ((wpos[sh] + wrk) & ((1u << mv.log_q) - 1u));
+  uint64_t rec;
+  if constexpr (FAST) {
+    rec = pack_rec8_fast(f, place, mbk, x0, x1);
+  } else {
+    const uint32_t wm = w8 & 0xffu, w0 = (w8 >> 8) & 0xffu;
+    const uint64_t z0 = ((uint64_t)x0 << 1) ^ (uint64_t)(x0 >> 63);
+    const uint64_t z1 = ((uint64_t)x1 << 1) ^ (uint64_t)(x1 >> 63);
+    rec = (uint64_t)place | ((uint64_t)mbk << 12) | (z0 << (12 + wm)) | (z1 << (12 + wm + w0));
+  }
+  *reinterpret_cast<uint64_t*>(reinterpret_cast<unsigned char*>(mv.rec) + (slot << 3)) = rec;
+}
 
 // Phase 4, per message i of the tile (the caller's unrolled loop over its items: the loop
 // inside a shared function cost every sort kernel 5 to 15 VGPRs): the record into its ring
@@ -717,6 +801,157 @@ struct DrainCounts {
   unsigned long long done = 0, failed = 0, holes = 0;
 };
 
+// The lean body of the narrow ring drain: a tile of 8-B records on a view of at most
+// kStatelessShards small rings (rings_small) with plain reply arrays (no rv.slots).
+//
+// Its runs (load_tile_runs8).  Wave 0 alone reads the tile's run words, scans the counts and
+// leaves in LDS the slot biases, the exclusive prefixes and, per group of 64 run entries (one
+// wave's share of one item), the shards of the group's first and last entry; one barrier.
+// No owner table and no fill loop (8 lanes wrote 4 KB of owner bytes while seven waves stood at
+// the barrier), no three-barrier vote, and the status stage, cleared ahead of that barrier,
+// needs no barriers of its own: a tile costs two barriers (was seven).
+struct Run8Lds {
+  uint32_t bias[kStatelessShards];  // ring slot of run entry j of shard s: s << log_q | ((bias[s] + j) & (Q - 1))
+  uint32_t excl[kStatelessShards];  // exclusive prefix of the counts (a shard the view lacks: the total)
+  uint32_t grp[(kST * kSK) / kWave];  // entries [64 g, 64 g + 64): shard of the first | shard of the last << 8
+  uint32_t total, spill;
+};
+template <int SK>
+__device__ __forceinline__ uint32_t load_tile_runs8(const MboxView& mv, const uint32_t* __restrict__ tinfo, uint32_t t,
+                                                    Run8Lds& R, int& spill) {
+  static_assert((kST * SK) / kWave <= kWave && kStatelessShards <= kWave, "one lane per group and per shard");
+  const uint32_t S = 1u << mv.log_s;
+  if (threadIdx.x < kWave) {  // (a whole wave)
+    const uint32_t lane = threadIdx.x;
+    uint32_t cnt = 0, bw = 0;
+    int sp = 0;
+    if (lane < S) {
+      const uint32_t cw = tinfo[(size_t)t * 2 * S + S + lane];
+      sp = (cw & kRunSpilled) != 0;
+      cnt = cw & ~kRunSpilled;
+      bw = tinfo[(size_t)t * 2 * S + lane];
+    }
+    const uint32_t incl = wave_incl_scan(cnt), ex = incl - cnt;
+    if (lane < kStatelessShards) {
+      R.bias[lane] = bw - ex;
+      R.excl[lane] = ex;
+    }
+    // entry j's shard: the number of shards 1.. whose runs start at or below j
+    const uint32_t jf = lane * kWave, jl = jf + (kWave - 1);
+    uint32_t sf = 0, sl = 0;
+#pragma unroll
+    for (int q = 1; q < (int)kStatelessShards; ++q) {
+      const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)ex, q);
+      sf += jf >= e, sl += jl >= e;
+    }
+    if (lane < (kST * SK) / kWave) R.grp[lane] = sf | (sl << 8);
+    const bool any_sp = __any(sp) != 0;
+    if (lane == kWave - 1) R.total = incl, R.spill = any_sp;
+  }
+  __syncthreads();
+  spill = (int)R.spill;
+  return R.total;
+}
+
+// The lean tile body behind its runs, for a tile that did not spill:
+//   owner by compare -- this wave's eight groups' shard pairs are read once into scalars; a group
+//   inside one run (all but at most seven of a tile's 64) takes its shard and bias as scalars, a
+//   group a run ends in compares its entries against the prefixes;
+//   slots and record addresses in 32 bits; fields decoded in 32 bits when the widths allow
+//   (rec8_fast: Multiply is then one 32 x 32 -> 64 multiply);
+//   the reply bounds tested once for the tile.
+template <int FIXED, int SK>
+__device__ __forceinline__ DrainCounts drain_ring_tile_lean(MboxView mv, SortIn in, uint32_t i0, uint32_t n_t, uint32_t T,
+                                                            const Run8Lds& R, int64_t* sval, uint8_t* sst,
+                                                            int64_t* __restrict__ state, uint32_t n_state,
+                                                            uint64_t delay_ticks, OutboxView ob, ReplyView rv) {
+  unsigned long long done = 0, failed = 0, holes = 0;
+  const uint32_t w8 = *in.r8w;
+  const Rec8Fast f = rec8_fast(w8);
+  const uint32_t qmask = (1u << mv.log_q) - 1u;
+  const unsigned char* recs = reinterpret_cast<const unsigned char*>(mv.rec);
+  const uint32_t wv = threadIdx.x / kWave, lane = lane_id();
+  // lanes 0..7: item k = lane's group of this wave (entries k * kST + wv * 64 ...), and shard lane's bias
+  const uint32_t gp = R.grp[(lane & (SK - 1)) * (kST / kWave) + wv];
+  const uint32_t bl = R.bias[lane & (kStatelessShards - 1)];
+  uint64_t ha[SK];
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {  // ring order: lane-consecutive entries of the runs
+    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
+    const uint32_t pair = (uint32_t)__builtin_amdgcn_readlane((int)gp, k);
+    const uint32_t sf = pair & 0xffu;
+    uint32_t slot;
+    if (sf == (pair >> 8)) {  // (wave-uniform)
+      const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)bl, sf);
+      slot = (sf << mv.log_q) | ((b + j) & qmask);
+    } else {
+      uint32_t s = 0;
+#pragma unroll
+      for (uint32_t q = 1; q < kStatelessShards; ++q) s += j >= R.excl[q];
+      slot = (s << mv.log_q) | ((R.bias[s] + j) & qmask);
+    }
+    if (j < T) ha[k] = *reinterpret_cast<const uint64_t*>(recs + (slot << 3));
+  }
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
+    if (j >= T) continue;
+    const uint32_t lo = (uint32_t)ha[k], hi = (uint32_t)(ha[k] >> 32);
+    const uint32_t local = lo & ((kST * SK) - 1);
+    if (local >= n_t) {  // never written this epoch (cannot happen on a spill-free tile)
+      ++holes;
+      continue;
+    }
+    MsgRecord m;
+    m.method = (uint16_t)(FIXED ? FIXED : in.method_uniform);
+    m.flags = 0;
+    m.a2 = 0;
+    if (f.ok) {
+      const uint32_t z0 = __builtin_amdgcn_alignbit(hi, lo, f.s0) & f.m0, z1 = hi >> f.s1h;
+      m.actor = (lo >> 12) & f.mm;
+      m.a0 = (int64_t)(int32_t)((z0 >> 1) ^ (0u - (z0 & 1u)));
+      m.a1 = (int64_t)(int32_t)((z1 >> 1) ^ (0u - (z1 & 1u)));
+    } else {
+      const SortRec x = decode_rec8<false, SK>(ha[k], in, w8, 0u);
+      m.actor = x.mb;
+      m.a0 = x.a0, m.a1 = x.a1;
+    }
+    const ReplyRecord rr = run_handler(m, state, n_state, delay_ticks, ob);
+    failed += rr.status != kStatusOk;
+    sval[local] = rr.value;
+    sst[local] = (uint8_t)rr.status;
+    ++done;
+  }
+  // (every record load is waited for here, on every path: see drain_ring_tile)
+  __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+  __syncthreads();
+  uint8_t rst[SK];
+  int64_t rval[SK];
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
+    rst[k] = j < n_t ? sst[j] : kAbsent;
+    rval[k] = sval[j];
+  }
+  // the tile's replies: its origins are o0 + j without wrapping and inside the reply arrays
+  const uint32_t o0 = in.origin_base + i0;
+  const bool whole = (uint64_t)o0 + (kST * SK) <= rv.n && (uint64_t)o0 + (kST * SK) <= 0x100000000ull;
+  int64_t* vb = rv.val + o0;
+  int32_t* sb = rv.st + o0;
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t j = (uint32_t)k * kST + threadIdx.x;
+    if (rst[k] == kAbsent) continue;
+    if (whole) {
+      __builtin_nontemporal_store(rval[k], vb + j);
+      __builtin_nontemporal_store((int32_t)rst[k], sb + j);
+    } else {
+      put_reply_nt(rv, o0 + j, rval[k], rst[k]);
+    }
+  }
+  return DrainCounts{done, failed, holes};
+}
+
 // (views and counts by value: references to a kernel's locals or arguments put
 // them in scratch)
 template <int FIXED, bool NARROW, bool FRESH, int RF = 0, int SK = kSK>
@@ -738,6 +973,23 @@ __device__ __forceinline__ DrainCounts drain_ring_tile(MboxView mv, SortIn in, u
   uint8_t* sst = NARROW ? reinterpret_cast<uint8_t*>(L.owner) : reinterpret_cast<uint8_t*>(L.owner + (kST * SK));
   const uint64_t i0 = (uint64_t)t * (kST * SK);
   const uint32_t n_t = (uint32_t)min((uint64_t)(kST * SK), (uint64_t)in.M - i0);
+  // the lean body (drain_ring_tile_lean) has no owner table: the status stage is its own from the start
+  constexpr bool kLeanForm = NARROW && RF == 1 && !FRESH;
+  if constexpr (kLeanForm) {
+    if (rv.slots == nullptr && S <= kStatelessShards && rings_small(mv)) {
+      __shared__ Run8Lds R8;
+      for (uint32_t j = threadIdx.x; j < (kST * SK); j += kST) sst[j] = kAbsent;
+      int spill8 = 0;
+      const uint32_t T8 = load_tile_runs8<SK>(mv, tinfo, t, R8, spill8);
+      if (spill8) {
+        drain_tile_msg<FIXED, FRESH, RF, SK>(mv, in, t, sidx, rw, state, n_state, delay_ticks, ob, rv, done, failed,
+                                             holes);
+        return DrainCounts{done, failed, holes};
+      }
+      return drain_ring_tile_lean<FIXED, SK>(mv, in, (uint32_t)i0, n_t, T8, R8, sval, sst, state, n_state, delay_ticks,
+                                             ob, rv);
+    }
+  }
   if constexpr (!NARROW)
     for (uint32_t j = threadIdx.x; j < (kST * SK); j += kST) sst[j] = kAbsent;
   int spill = 0;
