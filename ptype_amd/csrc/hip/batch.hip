@@ -203,6 +203,9 @@ __global__ __launch_bounds__(kRouteThreads) void route_prep_kernel(const uint32_
         if (a[k] < n_dir) {
           r[k] = aw_shift >= 0 ? (int)(a[k] & (aw - 1)) : (int)(a[k] % aw);
           mb[k] = aw_shift >= 0 ? a[k] >> aw_shift : a[k] / aw;
+        } else if (a[k] == 0xffffffffu) {  // the field that names no actor: never key 2^32
+          r[k] = -1;
+          mb[k] = 0;
         } else {
           lookup_entry(table, mask, actor_key(a[k]), r[k], mb[k]);
         }
@@ -210,7 +213,8 @@ __global__ __launch_bounds__(kRouteThreads) void route_prep_kernel(const uint32_
     } else if constexpr (DIR) {
       uint32_t w[K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) w[k] = a[k] < n_dir ? dir[a[k]] : kDirFallback;
+      for (int k = 0; k < K; ++k)  // (the field 0xffffffff names no actor: never a probe for key 2^32)
+        w[k] = a[k] < n_dir ? dir[a[k]] : a[k] == 0xffffffffu ? kDirMissing : kDirFallback;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         if (w[k] == kDirFallback) {
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(kRouteThreads) void route_prep_kernel(const uint32_
       uint64_t key[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) key[k] = actor_key(a[k]);
-      lookup_many<K>(table, mask, key, r, mb);
+      lookup_many<K>(table, mask, key, r, mb);  // (the field 0xffffffff resolves to nothing in there)
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {

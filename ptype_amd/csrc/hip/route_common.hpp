@@ -51,6 +51,9 @@ __device__ __forceinline__ void lookup_entry(const TableEntry* __restrict__ t, u
 // registry is L2/MALL resident, so a lookup is latency- not bandwidth-bound:
 // memory-level parallelism per thread is what hides it).  Keys that miss their
 // first group (rare at load factor <= 0.5) continue one at a time.
+// The keys are actor keys: actor_key(0xffffffff) = 2^32 resolves to nothing even when the
+// table holds that key, as the field 0xffffffff names no actor in any resolver.
+constexpr uint64_t kKeyNoActor = 1ull << 32;
 template <int K>
 __device__ __forceinline__ void lookup_many(const TableEntry* __restrict__ t, uint64_t mask, const uint64_t (&key)[K],
                                             int (&rank)[K], uint32_t (&mbox)[K]) {
@@ -65,7 +68,7 @@ __device__ __forceinline__ void lookup_many(const TableEntry* __restrict__ t, ui
   }
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    bool done = false;
+    bool done = key[k] == kKeyNoActor;
     rank[k] = -1;
     mbox[k] = 0;
 #pragma unroll

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(kRouteThreads) void route_fused_kernel(
     if constexpr (DIR) {
       uint32_t w[K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) w[k] = a[k] < n_dir ? dir[a[k]] : kDirFallback;
+      for (int k = 0; k < K; ++k)  // (the field 0xffffffff names no actor: never a probe for key 2^32)
+        w[k] = a[k] < n_dir ? dir[a[k]] : a[k] == 0xffffffffu ? kDirMissing : kDirFallback;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         if (w[k] == kDirFallback) {
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(kRouteThreads) void route_fused_kernel(
       uint64_t key[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) key[k] = actor_key(a[k]);
-      lookup_many<K>(table, mask, key, r, mb);
+      lookup_many<K>(table, mask, key, r, mb);  // (the field 0xffffffff resolves to nothing in there)
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {

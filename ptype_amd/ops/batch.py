@@ -267,8 +267,10 @@ def route(batch: MsgBatch, table: RegistryTable, R: int, C: int, rank_self: int 
     rank, mbox = table.lookup(actor_keys(actor))
     rank = rank.to(torch.int64)
     mbox = mbox.to(torch.int64)
-    ok = (rank >= 0) & (rank < R) & (mbox < MAX_MBOX)
-    cols = [mbox & 0xFFFFFFFF]
+    mbox = mbox & 0xFFFFFFFF  # unsigned, as the kernels compare it
+    # (the actor field 0xffffffff names no actor, even with key 2^32 in the table)
+    ok = (rank >= 0) & (rank < R) & (mbox < MAX_MBOX) & (actor != 0xFFFFFFFF)
+    cols = [mbox]
     if fmt.method_col:
         method = torch.full((M,), method_u, dtype=torch.int64) if uniform else batch.method.to(torch.int64)
         cols.append(method & 0xFFFF)

@@ -9,6 +9,19 @@ Reference semantics mirrored: ``Register`` puts a leased key under
 ``services/<svc>/<node>/`` (cluster/registry.go:51-86); lease expiry removes it
 (registry.go:59, TTL 2 s).  Keys here are 64-bit: actor id + 1 on the batch path
 (``actor_keys``), or a 64-bit FNV-1a of ``"<svc>/<node>"`` for service nodes.
+
+Generation (``stats[STAT_GEN]``, shown by ``Cluster.Stats()``) counts mutating calls,
+not changes, and both devices keep the same count: one per ``upsert`` / ``delete`` /
+``load_packed`` call that is given at least one row, one per ``sweep``, one per
+``clear``, whether or not the call changed anything; ``rebuild`` is a ``clear`` plus a
+``load_packed`` of what it kept.  A call with no rows leaves it alone.
+
+Not specified: which row wins when one upsert holds a key twice with different values
+(the value and the deadline kept may even come from different rows), which of two equal
+keys in one delete is reported found, and which slot of its probe chain a key takes when
+two keys with one probe start are inserted by one call -- the set of occupied slots is
+the same either way.  A table with no empty slot drops further new keys silently; the
+growth check of ``upsert`` / ``load_packed`` keeps callers away from that.
 """
 from __future__ import annotations
 
@@ -213,10 +226,9 @@ class RegistryTable:
             dead = (self.expiry != 0) & (self.expiry < now_ms) & (keys != KEY_EMPTY) & (keys != KEY_TOMB)
             n = int(dead.sum())
             keys[dead] = KEY_TOMB
-            if n:
-                self.stats[STAT_LIVE] -= n
-                self.stats[STAT_TOMB] += n
-                self.stats[STAT_GEN] += 1
+            self.stats[STAT_LIVE] -= n
+            self.stats[STAT_TOMB] += n
+            self.stats[STAT_GEN] += 1
 
     def pack(self):
         """K7: compact live entries -> (entries int64[n,2], expiry int64[n]) on the table's device."""
@@ -274,6 +286,7 @@ class RegistryTable:
             self.expiry = torch.zeros(self.cap, dtype=torch.int64, device=self.device)
             self.stats[STAT_LIVE] = 0
             self.stats[STAT_TOMB] = 0
+            self.stats[STAT_GEN] += 1  # the new arrays stand for the clear
         else:
             self.clear()
         if entries.numel():
@@ -345,7 +358,8 @@ class RegistryTable:
             maxp = max(maxp, probe)
         self.stats[STAT_LIVE] += added
         self.stats[STAT_MAXPROBE] = maxp
-        self.stats[STAT_GEN] += 1
+        if k_np.shape[0]:
+            self.stats[STAT_GEN] += 1
 
     def _cpu_delete(self, keys, found):
         tk, _ = self._slots()
@@ -368,9 +382,9 @@ class RegistryTable:
                     removed += 1
                     break
                 h = (h + 1) & mask
-        if removed:
-            self.stats[STAT_LIVE] -= removed
-            self.stats[STAT_TOMB] += removed
+        self.stats[STAT_LIVE] -= removed
+        self.stats[STAT_TOMB] += removed
+        if k_np.shape[0]:
             self.stats[STAT_GEN] += 1
 
     def _cpu_lookup(self, k_np: np.ndarray):

@@ -166,7 +166,8 @@ def test_gpu_table_matches_reference():
     c.upsert(keys, ranks, mbox)
     torch.cuda.synchronize()
     assert g.live == n == c.live
-    # same hash + same probing -> the slot images are identical for a single batch without duplicates
+    # same hash + same probing -> the same SET of occupied slots; two keys with one probe start may
+    # swap slots when one kernel inserts both, so only answers, never slot images, are compared here
     probe = torch.cat([keys[::3], torch.arange(10 * n + 5, 10 * n + 1000)])
     rg, mg = g.lookup(probe.cuda())
     rc, mc = c.lookup(probe)
