@@ -9,8 +9,8 @@ Builds two in-tree extension modules:
 * ``ptype_amd/_hip*.so`` -- HIP/CDNA4 device runtime (gfx950 only): HBM mailbox
   rings, GPU registry hash table, route/dispatch/complete kernels, persistent
   dispatcher, snapshot pack kernels, the Send wrappers' kernels (retry, ledger,
-  coalesce, reply cache, reply gather, circuit breaker, rate limiter), the call scatter of
-  ``Client.Ask``: every ``csrc/hip/*.hip``.
+  coalesce, reply cache, reply gather, circuit breaker, rate limiter, dead-letter queue), the
+  call scatter of ``Client.Ask``: every ``csrc/hip/*.hip``.
   Compiled with hipcc ``--offload-arch=gfx950``.
 
 Incremental: an object is rebuilt when its source or any header under ``csrc``

@@ -187,6 +187,7 @@ class Client:
         self._local_addr, self._max_connections = local_addr, int(max_connections)
         self._router = None  # replica routing of Send (parallel/replicas.py), when the service is replicated
         self._router_checked = False
+        self._tag = None  # FNV-1a64 of the service name: what this client's dead letters are filed under
 
     def _replica_router(self):
         if not self._router_checked:
@@ -203,7 +204,7 @@ class Client:
 
     def Send(self, batch, retries: int | None = None, retry_on=None, coalesce: bool | None = None,
              cache: bool | None = None, gather=None, breaker: bool | None = None, limit: bool | None = None,
-             **kw):
+             dead_letter: bool | None = None, **kw):
         """Batched submit of a ``MsgBatch`` to GPU actors of this service:
         RCCL epoch exchange across ranks, device dispatch, replies in order.
 
@@ -302,7 +303,23 @@ class Client:
         per Send (more passes and a second read only while some actor is over its quota), is
         refused under graph capture and never defers; ``Stats()["runtime"]["limit"]`` counts
         messages, throttled and sent ones.  Registry changes reset nothing, and limited
-        Sends must all be issued on one stream."""
+        Sends must all be issued on one stream.
+
+        ``dead_letter``: the dead-letter queue of an actor runtime (protoactor's
+        ``DeadLetterEvent``, Akka's ``deadLetters``) -- the messages that still failed after all
+        of the above (a final status in ``gpu.dead_letter_mask``, by default every failure
+        status 1 to 6) are filed with their whole call in a ring of ``gpu.dead_letter_entries``
+        64-byte records in HBM (ops/dead_letters.py), because ``batch`` is the caller's and
+        may be gone when anyone asks.  ``None`` follows ``gpu.dead_letters``, ``False`` skips
+        this Send, ``True`` without a queue raises.  It runs once, on the full batch's final
+        replies (a coalesced follower of a failed leader gets its own letter), costs two
+        kernel launches and no host read, is legal under graph capture and like an accounted
+        Send never defers its overflow re-sends.  The newest letters win: a ring that
+        overflows counts what it overwrote in ``dropped``.  ``DeadLetters()`` looks at the
+        queue, ``Redrive()`` re-sends it; ``Stats()["runtime"]["dead_letters"]`` counts.  The
+        queue belongs to the process's runtime, not to this client: letters are filed under
+        ``tag`` = FNV-1a64 of the client's service name, which is reported and not filtered
+        on."""
         if self._rt is None:
             raise RuntimeError("Client.Send needs the cluster's device runtime (Join with a gpu: section)")
         if retries:
@@ -317,7 +334,46 @@ class Client:
             kw.update(breaker=bool(breaker))
         if limit is not None:
             kw.update(limit=bool(limit))
+        if dead_letter is not None:
+            kw.update(dead_letter=bool(dead_letter))
+        if dead_letter is not False:  # (the tag of a Send that files nothing is not looked at)
+            kw.setdefault("dead_letter_tag", self._dead_letter_tag())
         return self._rt.send(self.service, batch, router=self._replica_router(), **kw)
+
+    def _dead_letter_tag(self) -> int:
+        if self._tag is None:
+            from .ops.dead_letters import fnv1a64
+
+            self._tag = fnv1a64(self.service)
+        return self._tag
+
+    def DeadLetters(self, max_letters: int | None = None, drain: bool = False):
+        """The unread letters of the runtime's dead-letter queue (at most ``max_letters``),
+        oldest first: an ``ops.dead_letters.Letters`` with the columns ``seq``, ``row``,
+        ``status``, ``actor``, ``method``, ``attempts``, ``a0``, ``a1``, ``a2`` and ``tag`` on the
+        device, ``n`` and ``torn``.  ``drain``: they leave the queue.  The queue is per runtime:
+        letters of every client of this process are in it, told apart by ``tag``."""
+        if self._rt is None:
+            raise RuntimeError("Client.DeadLetters needs the cluster's device runtime (Join with a gpu: section)")
+        return self._rt.dead_letters(max_letters, drain)
+
+    def Redrive(self, max_letters: int | None = None, **kw):
+        """The redrive of a message queue's dead-letter queue: up to ``max_letters`` letters
+        (and at most one Send's worth) are taken out of the runtime's queue and sent again
+        as one batch, through ``Send`` with every keyword it takes (``retries``, ``coalesce``,
+        ``cache``, ``breaker``, ``limit``, ``account``).  A letter that fails again is filed
+        again with ``attempts + 1`` and this client's tag, one that succeeds has left the
+        queue.  Returns an ``ops.dead_letters.Redrive``: ``letters``, ``value``, ``status``.
+        The queue is per runtime and the tag is not filtered on: ``Redrive`` sends whatever
+        it takes -- other clients' letters included -- to this client's own service.  The
+        keywords are checked before a letter is taken; an error the Send raises later than
+        that finds the letters taken, they are not put back.  It
+        reads the queue on the host (refused under graph capture) and is a collective Send
+        at world > 1."""
+        if self._rt is None:
+            raise RuntimeError("Client.Redrive needs the cluster's device runtime (Join with a gpu: section)")
+        kw.setdefault("dead_letter_tag", self._dead_letter_tag())
+        return self._rt.redrive(self.service, max_letters, router=self._replica_router(), **kw)
 
     def Ask(self, questions, scatter, op: str = "sum", sentinel=None, **kw):
         """Scatter-gather on the device: the optimus coordinator's ``splitWork`` ..
@@ -326,7 +382,7 @@ class Client:
         ``splitWork``, ``Scatter.members(offsets, members)`` one call to every member of a
         group -- expands the Q ``questions`` (a short ``MsgBatch``) into T calls with HIP
         kernels, the calls go through ``Send`` with every keyword it takes (``retries``,
-        ``coalesce``, ``cache``, ``breaker``, ``limit``, ``account``) and the replies are folded
+        ``coalesce``, ``cache``, ``breaker``, ``limit``, ``dead_letter``, ``account``) and the replies are folded
         per question with ``op`` (``sum``, ``min``, ``max`` or ``first_ne`` against
         ``sentinel``).  Returns an ``ops.scatter.Answer``: ``value``, ``status``, ``n_ok``,
         ``count`` and ``bad_row`` per question, the expansion's ``first``, ``n`` and ``oob``,
@@ -336,6 +392,8 @@ class Client:
         ``Stats()["runtime"]["scatter"]`` counts asks, questions, rows and oob."""
         if self._rt is None:
             raise RuntimeError("Client.Ask needs the cluster's device runtime (Join with a gpu: section)")
+        if kw.get("dead_letter") is not False:  # (as in Send: an Ask's letters carry this client's tag)
+            kw.setdefault("dead_letter_tag", self._dead_letter_tag())
         return self._rt.ask(self.service, questions, scatter, op=op, sentinel=sentinel, router=self._replica_router(),
                             **kw)
 
@@ -360,6 +418,7 @@ class Client:
         return self._c.connection_errs()
 
     call, go, send, tell, close, flush, ask = Call, Go, Send, Tell, Close, Flush, Ask
+    dead_letters, redrive = DeadLetters, Redrive
 
     @property
     def conns_updated(self) -> IntChannel:

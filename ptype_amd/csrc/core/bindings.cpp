@@ -345,6 +345,9 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("limit_rate", &GpuConfig::limit_rate)
       .def_readwrite("limit_burst", &GpuConfig::limit_burst)
       .def_readwrite("limit_actors", &GpuConfig::limit_actors)
+      .def_readwrite("dead_letters", &GpuConfig::dead_letters)
+      .def_readwrite("dead_letter_entries", &GpuConfig::dead_letter_entries)
+      .def_readwrite("dead_letter_mask", &GpuConfig::dead_letter_mask)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)

@@ -169,6 +169,19 @@ void decode_ptype(const YNode& root, Config& c) {
           if (n < 0 || n > (1ll << 28)) fail(Errc::kConfig, "gpu.limit_actors must be in [0, 2^28]");
           c.gpu.limit_actors = (uint64_t)n;
         }
+        else if (g.first == "dead_letters") c.gpu.dead_letters = want_bool(G, g.first, g.second);
+        else if (g.first == "dead_letter_entries") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 64 || n > (1ll << 24) || (n & (n - 1)))
+            fail(Errc::kConfig, "gpu.dead_letter_entries must be a power of two in [64, 2^24]");
+          c.gpu.dead_letter_entries = (uint64_t)n;
+        }
+        else if (g.first == "dead_letter_mask") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 2 || n > 0xffffffffll || (n & 1))
+            fail(Errc::kConfig, "gpu.dead_letter_mask must be in [2, 2^32) with bit 0 (STATUS_OK) clear");
+          c.gpu.dead_letter_mask = (uint64_t)n;
+        }
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

@@ -16,6 +16,7 @@
 #include "ipc_comm.hpp"
 #include "gather.hpp"
 #include "scatter.hpp"
+#include "dead_letters.hpp"
 #include "ledger.hpp"
 #include "limit.hpp"
 #include "mailbox.hpp"
@@ -113,6 +114,11 @@ void launch_retry_merge(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uin
 int64_t ledger_tile();
 void launch_ledger_account(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t,
                            uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
+int64_t dlq_tile();
+void launch_dlq_append(uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t,
+                       uintptr_t, int64_t, uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
+void launch_dlq_take(uintptr_t, uintptr_t, int64_t, int64_t, int64_t, bool, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                     uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
 int64_t coalesce_tile();
 void launch_coalesce_group(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int,
                            uintptr_t, uintptr_t);
@@ -392,6 +398,46 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("load"), py::arg("n_load"), py::arg("ticket"), py::arg("stream"),
         "one pass over a Send's replies and batch columns into ledger (copies x words of ledger_words() int64), the optional "
         "per-actor load table (n_load int64) and sends; ticket: ledger_words()['ticket_words'] zeroed u32");
+
+  // ---- dead-letter queue (dead_letters.hip, dead_letters.hpp): a Send's failed calls kept in an HBM ring
+  m.def("dead_letter_layout", []() {
+    py::dict rec, ctl, d;
+    rec["ticket"] = kDlqTicket;
+    rec["seq"] = kDlqSeq;
+    rec["row_status"] = kDlqRowStatus;
+    rec["actor_method_attempts"] = kDlqActorMethodAttempts;
+    rec["a0"] = kDlqA0;
+    rec["a1"] = kDlqA1;
+    rec["a2"] = kDlqA2;
+    rec["tag"] = kDlqTag;
+    ctl["head"] = kDlqHead;
+    ctl["tail"] = kDlqTail;
+    ctl["dropped"] = kDlqDropped;
+    ctl["sends"] = kDlqSends;
+    ctl["base"] = kDlqBase;
+    ctl["torn"] = kDlqTorn;
+    ctl["seq"] = kDlqSeqNext;
+    d["record"] = rec;
+    d["control"] = ctl;
+    d["record_words"] = kDlqRecordWords;
+    d["control_words"] = kDlqCtrlWords;
+    d["tile"] = dlq_tile();
+    d["min_entries"] = kDlqMinEntries;
+    d["max_entries"] = kDlqMaxEntries;
+    d["max_attempts"] = kDlqMaxAttempts;
+    return d;
+  }, "u64 word indices of a dead-letter record and of the control line (dead_letters.hpp), and the sizes");
+  m.def("dlq_append", &launch_dlq_append, py::arg("status"), py::arg("M"), py::arg("mask"), py::arg("actor"),
+        py::arg("method_col"), py::arg("method_uniform"), py::arg("attempts"), py::arg("a0"), py::arg("a1"),
+        py::arg("a2"), py::arg("tag"), py::arg("ring"), py::arg("ctrl"), py::arg("entries"), py::arg("counts"),
+        py::arg("stream"),
+        "file the rows whose status bit is set in mask into the ring, tickets in row order (two launches, no host read); "
+        "counts: max(1, ceil(M / tile)) u32 words of workspace");
+  m.def("dlq_take", &launch_dlq_take, py::arg("ring"), py::arg("ctrl"), py::arg("entries"), py::arg("t0"), py::arg("n"),
+        py::arg("drain"), py::arg("seq"), py::arg("row"), py::arg("status"), py::arg("actor"), py::arg("method"),
+        py::arg("attempts"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("tag"), py::arg("stream"),
+        "n letters from ticket t0 into SoA columns; mismatching ticket words counted in the control line's torn; "
+        "drain: tail = t0 + n");
 
   // ---- Send coalescing (coalesce.hip, coalesce.hpp): duplicates of a pure call are sent once
   m.def("coalesce_tile", &coalesce_tile, "messages per block of coalesce_group's insert kernel");

@@ -2,7 +2,9 @@
 // gathered, in index order, into a sub-batch.  Two instances: retry.hip selects by
 // status (the retries, and the reply cache's, the breaker's and the limiter's
 // kPending rows), coalesce.hip selects the group leaders (lead[i] == i) and also
-// wants every row's place in the sub-batch.
+// wants every row's place in the sub-batch.  dead_letters.hip ranks its tiles with the
+// same device helpers (compact_tile_ballots / _offsets / compact_lane_rank) and writes
+// ring records instead of a sub-batch.
 //
 //   compact_count_kernel   launch 1: one block per tile of kCompactTile keys; the
 //                          tile's number of selected rows goes to counts[tile]
@@ -43,19 +45,65 @@ struct OwnIndex {  // the key is the row's own index
   __device__ __forceinline__ bool operator()(int l, int i) const { return l == i; }
 };
 
-// The four keys at element index i (a multiple of 4; `key` is 16-byte aligned).
-// Elements at or past M read as -1: never selected, by either predicate.
+// The four keys at element index i (a multiple of 4).  With VEC `key` is 16-byte
+// aligned and four keys inside M come by one dwordx4 load; without it (a view at an
+// odd offset) every key is a load of its own.  Elements at or past M read as -1:
+// never selected, by either predicate.
+template <bool VEC = true>
 __device__ __forceinline__ int4 compact_load4(const int* __restrict__ key, int64_t i, int64_t M) {
-  if (i + 4 <= M) return *reinterpret_cast<const int4*>(key + i);
+  if constexpr (VEC) {
+    if (i + 4 <= M) return *reinterpret_cast<const int4*>(key + i);
+  }
   int4 v = {-1, -1, -1, -1};
   if (i < M) v.x = key[i];
   if (i + 1 < M) v.y = key[i + 1];
   if (i + 2 < M) v.z = key[i + 2];
+  if constexpr (!VEC) {
+    if (i + 3 < M) v.w = key[i + 3];
+  }
   return v;
 }
 
 __device__ __forceinline__ int64_t compact_elem(int64_t tile, int j, unsigned wave, unsigned lane) {
   return tile * kCompactTile + (int64_t)(j * kCompactWaves + (int)wave) * (kWave * 4) + lane * 4;
+}
+
+// Ranking of one tile, shared by compact_select_kernel and the dead-letter append
+// (dead_letters.hip).  Step 1: the four ballots of each of this wave's segments, and the
+// segments' counts into seg_cnt[kCompactSegs] (LDS); a __syncthreads() follows.
+template <class Pred, bool VEC = true>
+__device__ __forceinline__ void compact_tile_ballots(const int* __restrict__ key, int64_t M, Pred pred, int64_t tile,
+                                                     unsigned wave, unsigned lane, uint64_t (&b)[kCompactLoads][4],
+                                                     unsigned* __restrict__ seg_cnt) {
+#pragma unroll
+  for (int j = 0; j < kCompactLoads; ++j) {
+    const int64_t i = compact_elem(tile, j, wave, lane);
+    const int4 v = compact_load4<VEC>(key, i, M);
+    b[j][0] = __ballot(pred(v.x, (int)i));
+    b[j][1] = __ballot(pred(v.y, (int)i + 1));
+    b[j][2] = __ballot(pred(v.z, (int)i + 2));
+    b[j][3] = __ballot(pred(v.w, (int)i + 3));
+    if (lane == 0)
+      seg_cnt[j * kCompactWaves + wave] =
+          __popcll(b[j][0]) + __popcll(b[j][1]) + __popcll(b[j][2]) + __popcll(b[j][3]);
+  }
+}
+// Step 2: the rank within the tile at which each of this wave's segments starts; returns
+// the tile's number of selected rows.
+__device__ __forceinline__ unsigned compact_tile_offsets(const unsigned* __restrict__ seg_cnt, unsigned wave,
+                                                         unsigned (&seg_off)[kCompactLoads]) {
+  unsigned total = 0;
+#pragma unroll
+  for (int s = 0; s < kCompactSegs; ++s) {  // (LDS broadcast reads; s = j * kCompactWaves + wave)
+    if ((s % kCompactWaves) == (int)wave) seg_off[s / kCompactWaves] = total;
+    total += seg_cnt[s];
+  }
+  return total;
+}
+// Step 3: the rank within the tile of this lane's first selected element of segment j
+// (selected elements of lower lanes come first, then this lane's lower components).
+__device__ __forceinline__ unsigned compact_lane_rank(const uint64_t (&bj)[4], unsigned seg_off_j) {
+  return seg_off_j + mbcnt64(bj[0]) + mbcnt64(bj[1]) + mbcnt64(bj[2]) + mbcnt64(bj[3]);
 }
 
 template <class Pred>
@@ -103,32 +151,16 @@ __global__ __launch_bounds__(kCompactThreads) void compact_select_kernel(
 
   // rank the tile: per 256-element segment, four ballots
   uint64_t b[kCompactLoads][4];
-#pragma unroll
-  for (int j = 0; j < kCompactLoads; ++j) {
-    const int64_t i = compact_elem(tile, j, wave, lane);
-    const int4 v = compact_load4(key, i, M);
-    b[j][0] = __ballot(pred(v.x, (int)i));
-    b[j][1] = __ballot(pred(v.y, (int)i + 1));
-    b[j][2] = __ballot(pred(v.z, (int)i + 2));
-    b[j][3] = __ballot(pred(v.w, (int)i + 3));
-    if (lane == 0)
-      seg_cnt[j * kCompactWaves + wave] =
-          __popcll(b[j][0]) + __popcll(b[j][1]) + __popcll(b[j][2]) + __popcll(b[j][3]);
-  }
+  compact_tile_ballots(key, M, pred, tile, wave, lane, b, seg_cnt);
   __syncthreads();
   unsigned off = 0;
 #pragma unroll
   for (int w = 0; w < kCompactWaves; ++w) off += wave_sum[w];
-  unsigned seg_off[kCompactLoads], total = 0;
-#pragma unroll
-  for (int s = 0; s < kCompactSegs; ++s) {  // (LDS broadcast reads; s = j * kCompactWaves + wave)
-    if ((s % kCompactWaves) == (int)wave) seg_off[s / kCompactWaves] = total;
-    total += seg_cnt[s];
-  }
+  unsigned seg_off[kCompactLoads];
+  const unsigned total = compact_tile_offsets(seg_cnt, wave, seg_off);
 #pragma unroll
   for (int j = 0; j < kCompactLoads; ++j) {
-    // selected elements of lower lanes come first, then this lane's lower components
-    unsigned r = seg_off[j] + mbcnt64(b[j][0]) + mbcnt64(b[j][1]) + mbcnt64(b[j][2]) + mbcnt64(b[j][3]);
+    unsigned r = compact_lane_rank(b[j], seg_off[j]);
     const int64_t i = compact_elem(tile, j, wave, lane);
     int p[4];
 #pragma unroll

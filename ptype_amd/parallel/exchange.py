@@ -427,7 +427,7 @@ class ActorExchange:
         return dist.all_to_all_single(out, inp, group=self.group, async_op=True)
 
     def send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None,
-             ledger=None, gather=None):
+             ledger=None, gather=None, dead_letters=None):
         """Deliver every message of ``req`` (a SoA ``MsgBatch``) to its actor and return
         ``(value int64[M], status int32[M])`` in message order.  Collective:
         every rank of the group must call it (with its own, possibly empty, batch)
@@ -435,7 +435,9 @@ class ActorExchange:
         this Send's replies -- one more kernel on the Send's own stream (no stream
         fork, no host read; capturable).  ``gather``: an ``ops.gather.Gather`` that folds
         this Send's replies into its groups -- two more kernels on the same stream,
-        capturable alike."""
+        capturable alike.  ``dead_letters``: an ``ops.dead_letters.DeadLetters`` (or its
+        ``bound`` sink) that files this Send's failed rows in its ring -- two more kernels
+        on the same stream, capturable alike; every replay files them again."""
         if gather is not None:
             gather.check_batch(req.M)
         val, st = self._send(req, out_val, out_status)
@@ -443,6 +445,8 @@ class ActorExchange:
             ledger.account(req, val, st)
         if gather is not None:
             gather.reduce(val, st)
+        if dead_letters is not None:
+            dead_letters.append(req, st)
         return val, st
 
     def _send(self, req: B.MsgBatch, out_val: torch.Tensor | None = None, out_status: torch.Tensor | None = None):
@@ -541,7 +545,8 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def capture(self, req: B.MsgBatch, out_val: torch.Tensor, out_status: torch.Tensor, prologue=None,
-                allow_collectives: bool = False, repeat: int = 1, ledger=None, gather=None) -> "SendGraph":
+                allow_collectives: bool = False, repeat: int = 1, ledger=None, gather=None,
+                dead_letters=None) -> "SendGraph":
         """Capture ``send(req)`` (plus an optional ``prologue()``, e.g. a kernel
         that refills ``req``) into a hipGraph for fixed-shape steady-state epochs:
         one graph launch replaces the ~6 kernel launches + host logic per chunk,
@@ -551,10 +556,11 @@ class ActorExchange:
         the step's index j within the replay.  Single rank by default;
         RCCL collectives are capturable but opt-in (``allow_collectives``).
         ``ledger``: every captured step is accounted (see ``SendGraph``); ``gather``:
-        every captured step is gathered."""
+        every captured step is gathered; ``dead_letters``: every captured step files its
+        failed rows."""
         if (self.world > 1 or self.force_collectives) and not allow_collectives:
             raise RuntimeError("capture: collectives in a graph are opt-in (allow_collectives=True)")
-        return SendGraph(self, req, out_val, out_status, prologue, repeat, ledger, gather)
+        return SendGraph(self, req, out_val, out_status, prologue, repeat, ledger, gather, dead_letters)
 
     # ------------------------------------------------------------------
     def pump(self, outbox, initial: B.MsgBatch | None = None, max_epochs: int = 1 << 20, check_every: int = 8):
@@ -781,7 +787,8 @@ class ActorExchange:
 
     # ------------------------------------------------------------------
     def send_all(self, req: B.MsgBatch, max_epochs: int = 16, out: tuple | None = None, defer: bool = False,
-                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None, ledger=None, gather=None):
+                 retries: int = 0, retry_on=(STATUS_FAILED,), reroute=None, logical=None, ledger=None, gather=None,
+                 dead_letters=None):
         """`send` + re-send of overflowed messages until every one is delivered.
         Reads the overflow count once per epoch (a host round trip); with adaptive
         slot capacity (native engine, wire v3) skewed traffic fits in the first
@@ -822,17 +829,23 @@ class ActorExchange:
 
         ``gather``: an ``ops.gather.Gather`` that folds this Send's final replies into
         its groups, once, at the same point as the ledger.  Like an accounted Send, a
-        gathered Send never defers its overflow re-sends."""
-        if ledger is not None or gather is not None:
+        gathered Send never defers its overflow re-sends.
+
+        ``dead_letters``: an ``ops.dead_letters.DeadLetters`` (or its ``bound`` sink) that files
+        the rows that still failed in its ring, once, at the same point and under ``logical``
+        actor ids alike; such a Send never defers either."""
+        if ledger is not None or gather is not None or dead_letters is not None:
             if gather is not None:
                 gather.check_batch(req.M)
             val, st = self.send_all(req, max_epochs, out, False, retries, retry_on, reroute, logical)
+            if logical is not None and (ledger is not None or dead_letters is not None):
+                req = B.MsgBatch(logical.to(torch.int32), req.a0, req.a1, req.a2, req.method)
             if ledger is not None:
-                if logical is not None:
-                    req = B.MsgBatch(logical.to(torch.int32), req.a0, req.a1, req.a2, req.method)
                 ledger.account(req, val, st)
             if gather is not None:
                 gather.reduce(val, st)
+            if dead_letters is not None:
+                dead_letters.append(req, st)
             return val, st
         retries = int(retries)
         if retries < 0:
@@ -1089,10 +1102,13 @@ class SendGraph:
     ledger kernel is one more node on the Send's own stream: no parallel branch).
     The two warm-up sends before the capture are accounted too: ``reset()`` the
     ledger after building the graph.  ``gather``: an ``ops.gather.Gather`` handed to
-    the captured ``send`` alike: its outputs hold the last step's groups after a replay."""
+    the captured ``send`` alike: its outputs hold the last step's groups after a replay.
+    ``dead_letters``: an ``ops.dead_letters.DeadLetters`` handed to the captured ``send``
+    alike: every replayed step files its failed rows (``reset()`` it after building the
+    graph to count from there)."""
 
     def __init__(self, ex: ActorExchange, req: B.MsgBatch, out_val, out_status, prologue=None, repeat: int = 1,
-                 ledger=None, gather=None):
+                 ledger=None, gather=None, dead_letters=None):
         if repeat < 1:
             raise ValueError("repeat >= 1")
         self.ex, self.req, self.M, self.repeat = ex, req, req.M, int(repeat)
@@ -1104,7 +1120,7 @@ class SendGraph:
                     prologue(j)  # the step's index within the replay
                 else:
                     prologue()
-            ex.send(req, out_val, out_status, ledger, gather)
+            ex.send(req, out_val, out_status, ledger, gather, dead_letters)
 
         def body():
             for j in range(self.repeat):

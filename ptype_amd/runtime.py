@@ -75,7 +75,8 @@ class DeviceRuntime:
                  ledger: bool = False, coalesce: bool = False, cache: bool = False, cache_entries: int = 1 << 20,
                  breaker: bool = False, breaker_threshold: int = 5, breaker_cooldown: int = 8,
                  breaker_actors: int = 0, breaker_trip_on=None, limit: bool = False, limit_rate: int = 1,
-                 limit_burst: int = 1, limit_actors: int = 0):
+                 limit_burst: int = 1, limit_actors: int = 0, dead_letters: bool = False,
+                 dead_letter_entries: int = 1 << 16, dead_letter_mask=None):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -176,6 +177,17 @@ class DeviceRuntime:
             raise ValueError("limit_actors must be >= 0 (0: every actor of the service)")
         LimiterRef("cpu", 1, self.limit_rate, self.limit_burst)  # (validates the settings)
         self._limiter = None
+        # Dead-letter queue (ops/dead_letters.py, opt-in): the default of send(dead_letter=None);
+        # the calls whose final status is in the mask, kept whole in an HBM ring until they are
+        # looked at (dead_letters()) or re-sent (redrive())
+        from .ops import dead_letters as DL
+
+        self.dead_letter_entries = DL.check_entries(dead_letter_entries)
+        self.dead_letter_mask = DL.dead_letter_mask(dead_letter_mask)
+        self._dlq = None
+        if dead_letters:
+            self._dlq = DL.DeadLetters(self.device, self.dead_letter_entries, self.dead_letter_mask,
+                                       max_rows=self.max_batch)
         # Scatter-gather (ask, ops/scatter.py): host counters, from what every expansion read
         self._scatter_counters = {"asks": 0, "questions": 0, "rows": 0, "oob": 0}
         self.shards: dict[str, list[dict]] = {}
@@ -245,7 +257,8 @@ class DeviceRuntime:
                  cache=g.cache, cache_entries=g.cache_entries, breaker=g.breaker,
                  breaker_threshold=g.breaker_threshold, breaker_cooldown=g.breaker_cooldown,
                  breaker_actors=g.breaker_actors, limit=g.limit, limit_rate=g.limit_rate,
-                 limit_burst=g.limit_burst, limit_actors=g.limit_actors)
+                 limit_burst=g.limit_burst, limit_actors=g.limit_actors, dead_letters=g.dead_letters,
+                 dead_letter_entries=g.dead_letter_entries, dead_letter_mask=g.dead_letter_mask or None)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -398,9 +411,25 @@ class DeviceRuntime:
     def send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
              retries: int | None = None, retry_on=None, account: bool | None = None,
              coalesce: bool | None = None, cache: bool | None = None, gather=None, breaker: bool | None = None,
-             limit: bool | None = None):
+             limit: bool | None = None, dead_letter: bool | None = None, dead_letter_tag: int = 0,
+             dead_letter_attempts=None):
         """Batched Send (``_send``), optionally coalesced, answered from the reply cache,
         guarded by the circuit breaker and rate-limited per actor.
+        ``dead_letter``: the rows whose final status is in the runtime's ``dead_letter_mask``
+        (by default statuses 1 to 6) are filed, with the whole call, in the runtime's
+        dead-letter queue in HBM (ops/dead_letters.py: protoactor's ``DeadLetterEvent``,
+        Akka's ``deadLetters``), under the ids the caller wrote, with ``dead_letter_tag`` and
+        ``dead_letter_attempts`` (an int32 column: earlier attempts of each row; None: none).
+        None follows the runtime's setting (``DeviceRuntime(dead_letters=...)``,
+        ``gpu.dead_letters``), False skips this Send, True without a queue raises.  It runs
+        once per Send, on the full batch's final replies, where the ledger and the gather
+        do: after coalescing's fan-out (a failed leader's followers each get a letter), the
+        cache hits, the breaker's and the limiter's answers, the retries and the overflow
+        re-sends.  Like an accounted Send it never defers its overflow re-sends.  It is the
+        caller's view (no collective), reads nothing on the host and allocates nothing, so
+        it does not by itself forbid graph capture; every replay files its letters again.
+        ``dead_letters()`` looks at the queue, ``redrive()`` re-sends it.  Without it a Send
+        creates, launches and reads nothing new.
         ``gather``: an ``ops.gather.Gather`` over this batch -- the replies are folded
         into its groups on the device (sum / min / max / first_ne per group, the first
         error per group), once per Send, on the full batch's final replies in the
@@ -508,8 +537,10 @@ class DeviceRuntime:
             limit = self.limit
         if gather is not None:
             gather.check_batch(batch.M)
+        dlq = self._dead_letter_sink(dead_letter, dead_letter_attempts, dead_letter_tag)
         if not coalesce and not cache and not breaker and not limit:
-            return self._send(service, batch, resend_overflow, router, retries, retry_on, account, gather=gather)
+            return self._send(service, batch, resend_overflow, router, retries, retry_on, account, gather=gather,
+                              dead_letters=dlq)
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
@@ -560,12 +591,23 @@ class DeviceRuntime:
                 self._cache_seen = seen
             inner = wrap(self._cache, inner)
         if not coalesce:
-            return self._settle(batch, inner(batch), ledger, gather)
+            return self._settle(batch, inner(batch), ledger, gather, dead_letters=dlq)
         if self._coalescer is None:
             from .ops.coalesce import Coalescer
 
             self._coalescer = Coalescer(self.device, self.max_batch)
-        return self._settle(batch, self._coalescer.send(batch, inner)[0], ledger, gather)
+        return self._settle(batch, self._coalescer.send(batch, inner)[0], ledger, gather, dead_letters=dlq)
+
+    def _dead_letter_sink(self, dead_letter: bool | None, attempts=None, tag: int = 0):
+        """The dead-letter queue with one Send's ``attempts`` and ``tag`` bound, or None."""
+        if dead_letter is None:
+            dead_letter = self._dlq is not None
+        if not dead_letter:
+            return None
+        if self._dlq is None:
+            raise ValueError("send(dead_letter=True): this runtime keeps no dead-letter queue "
+                             "(DeviceRuntime(dead_letters=True), gpu.dead_letters)")
+        return self._dlq.bound(attempts, tag)
 
     def _existence_stamp(self, service: str | None, router):
         """What decides whether an actor exists, brought up to date: the registry change
@@ -579,22 +621,98 @@ class DeviceRuntime:
             self._check_service(service)
         return self._registry_changes, router, None if router is None else router.changes
 
-    def _settle(self, batch: B.MsgBatch, out, ledger, gather, logical=None):
+    def _settle(self, batch: B.MsgBatch, out, ledger, gather, logical=None, dead_letters=None):
         """A Send's final replies into the ledger (``batch`` under its ``logical`` actor
-        ids, when a router rewrote them) and the gather; returns ``out``."""
+        ids, when a router rewrote them), the gather and the dead-letter queue (under the
+        logical ids too); returns ``out``."""
         if ledger is not None:
             ledger.account(batch if logical is None else self._logical_batch(batch, logical), out[0], out[1])
         if gather is not None:
             gather.reduce(out[0], out[1])
+        if dead_letters is not None:
+            dead_letters.append(batch if logical is None else self._logical_batch(batch, logical), out[1])
         return out
+
+    def dead_letters(self, max_letters: int | None = None, drain: bool = False):
+        """The unread letters of the dead-letter queue (at most ``max_letters``), oldest
+        first, as an ``ops.dead_letters.Letters``: SoA columns on the device (``seq``, ``row``,
+        ``status``, ``actor``, ``method``, ``attempts``, ``a0``, ``a1``, ``a2``, ``tag``) with ``n``
+        and ``torn``.  ``drain``: they leave the queue.  Reads the queue's head and tail on
+        the host."""
+        if self._dlq is None:
+            raise ValueError("dead_letters(): this runtime keeps no dead-letter queue "
+                             "(DeviceRuntime(dead_letters=True), gpu.dead_letters)")
+        return self._dlq.take(max_letters, drain)
+
+    def redrive(self, service: str | None, max_letters: int | None = None, router=None, **send_kw):
+        """Re-send the dead letters: up to ``min(unread, max_letters, max_batch)`` of them are
+        taken out of the queue, oldest first, and sent as one batch of the logical ids their
+        callers wrote -- through ``send`` with every keyword it takes (``send_kw``), and with
+        dead-lettering on, the letters' ``attempts`` and the caller's ``dead_letter_tag``: a
+        letter that fails again is back in the queue with ``attempts + 1``, one that succeeds
+        has left it.  Returns an ``ops.dead_letters.Redrive``: the taken ``letters`` and the
+        re-send's ``(value, status)``, row for row.  It reads the queue on the host, so it is
+        refused under graph capture.  At world > 1 it is a collective Send like any other (a
+        rank without letters joins with an empty batch); at world 1 without letters the Send
+        is skipped.  The keywords are checked before a letter is taken -- an unknown one,
+        ``account=True`` without a ledger, a ``gather`` of another size than the letters to
+        take, ``retries`` with ``resend_overflow=False`` or a bad ``retry_on``, a service this
+        runtime does not host -- so such a call leaves the queue as it was.  An error the
+        Send raises later than that (letters of an ordered method re-sent with ``retries``,
+        a rank failure that is not recovered) finds the letters already taken: they are not
+        put back."""
+        import inspect
+
+        from .ops.dead_letters import Redrive
+        from .ops.retry import retry_mask
+
+        if self._dlq is None:
+            raise ValueError("redrive(): this runtime keeps no dead-letter queue "
+                             "(DeviceRuntime(dead_letters=True), gpu.dead_letters)")
+        if "dead_letter" in send_kw or "dead_letter_attempts" in send_kw:
+            raise ValueError("redrive: dead-lettering of the re-send is its own (attempts, dead_letter=True)")
+        if (self._exchange is not None and self._exchange._capturing) or (
+                self.on_gpu and torch.cuda.is_current_stream_capturing()):
+            raise ValueError("redrive inside a captured Send: the queue's head and tail are read on the host")
+        # what send would refuse, before a letter leaves the queue
+        inspect.signature(self.send).bind(service, None, router=router, **send_kw)  # (an unknown keyword: TypeError)
+        if send_kw.get("account") and self.ledger is None:
+            raise ValueError("redrive(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
+                             "gpu.ledger)")
+        if send_kw.get("retries"):
+            if int(send_kw["retries"]) < 0:
+                raise ValueError("retries >= 0")
+            if not send_kw.get("resend_overflow", True):
+                raise ValueError("redrive(retries > 0) runs after the overflow re-sends: resend_overflow=False "
+                                 "excludes it")
+            if send_kw.get("retry_on") is not None:
+                retry_mask(send_kw["retry_on"])
+        if router is None:
+            self._check_service(service)
+        ex = self.exchange
+        n = min(self._dlq.read()["unread"], ex.max_chunk * ex.chunks)
+        if max_letters is not None:
+            n = min(n, max(0, int(max_letters)))
+        if send_kw.get("gather") is not None:
+            send_kw["gather"].check_batch(n)
+        letters = self._dlq.take(n, drain=True)
+        self._dlq.counters["redrives"] += 1
+        self._dlq.counters["redriven"] += letters.n
+        if letters.n or self.world > 1:
+            out = self.send(service, letters.batch(), router=router, dead_letter=True,
+                            dead_letter_attempts=letters.attempts, **send_kw)
+        else:
+            out = (torch.empty(0, dtype=torch.int64, device=self.device),
+                   torch.empty(0, dtype=torch.int32, device=self.device))
+        return Redrive(letters, out[0], out[1])
 
     def ask(self, service: str | None, questions: B.MsgBatch, scatter, op: str = "sum", sentinel=None, **send_kw):
         """Scatter-gather in one call (the optimus coordinator's ``splitWork`` ..
         ``watchReplies``, coordinator.go:67-98): ``scatter`` (an ``ops.scatter.Scatter``)
         expands the Q ``questions`` into T calls on the device, the calls go through
         ``send`` -- ``send_kw`` is its keywords, so ``retries``, ``coalesce``, ``cache``,
-        ``breaker``, ``limit``, ``account``, ``router`` and ``resend_overflow`` apply to the
-        expanded calls exactly as to any batch -- and the expansion's ``Gather`` folds the
+        ``breaker``, ``limit``, ``dead_letter``, ``account``, ``router`` and ``resend_overflow`` apply
+        to the expanded calls exactly as to any batch -- and the expansion's ``Gather`` folds the
         replies with ``op`` (``sentinel`` for ``first_ne``) into one answer per question.
         Returns an ``ops.scatter.Answer``.  The expansion reads its total on the host, so
         an Ask is refused under graph capture; more calls than a Send takes raise the
@@ -646,7 +764,7 @@ class DeviceRuntime:
 
     def _send(self, service: str | None, batch: B.MsgBatch, resend_overflow: bool = True, router=None,
               retries: int | None = None, retry_on=None, account: bool | None = None, final: bool = False,
-              gather=None):
+              gather=None, dead_letters=None):
         """Batched Send: every message to its actor anywhere in the node and the
         replies back in message order.  Collective across the process group.
         Registry changes seen since the last Send are applied first.  With an
@@ -665,7 +783,9 @@ class DeviceRuntime:
         ``final``: the replies must be final on return (a coalesced Send fans them
         out): the overflow re-sends are not deferred.
         ``gather``: an ``ops.gather.Gather`` that folds the final replies into its groups
-        (``send``); a gathered Send does not defer its overflow re-sends either."""
+        (``send``); a gathered Send does not defer its overflow re-sends either.
+        ``dead_letters``: the dead-letter queue's sink of this Send (``send(dead_letter=)``): the
+        final replies' failed rows are filed there, at the same point, never deferred."""
         if account and self.ledger is None:
             raise ValueError("send(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
                              "gpu.ledger)")
@@ -685,10 +805,12 @@ class DeviceRuntime:
         self.sync()
         if self.membership is None:
             ex = self.exchange
-            if ledger is not None or gather is not None:  # on its final replies: never deferred
+            if ledger is not None or gather is not None or dead_letters is not None:
+                # on its final replies: never deferred
                 if resend_overflow:
-                    return ex.send_all(batch, logical=logical, ledger=ledger, gather=gather, **rkw)
-                return self._settle(batch, ex.send(batch), ledger, gather, logical)
+                    return ex.send_all(batch, logical=logical, ledger=ledger, gather=gather,
+                                       dead_letters=dead_letters, **rkw)
+                return self._settle(batch, ex.send(batch), ledger, gather, logical, dead_letters)
             # more than one rank: no host wait on this Send (its overflow, if any, is
             # re-sent just before Send + 2 or at flush(): ActorExchange.send_all)
             if rkw:
@@ -749,13 +871,13 @@ class DeviceRuntime:
                         raise
                     self.recover()  # the batch WAS delivered: recover, never re-send it
             if todo is None:
-                return self._settle(batch, out, ledger, gather, logical)
+                return self._settle(batch, out, ledger, gather, logical, dead_letters)
             val = torch.zeros(batch.M, dtype=out[0].dtype, device=out[0].device)
             st = torch.full((batch.M,), STATUS_RANK_LOST, dtype=out[1].dtype, device=out[1].device)
             val[todo] = out[0]
             st[todo] = out[1]
             # the whole batch, the STATUS_RANK_LOST rows included
-            return self._settle(batch, (val, st) + tuple(out[2:]), ledger, gather, logical)
+            return self._settle(batch, (val, st) + tuple(out[2:]), ledger, gather, logical, dead_letters)
         raise AssertionError("unreachable")
 
     @staticmethod
@@ -1101,6 +1223,9 @@ class DeviceRuntime:
             out["limit"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "throttled": 0, "oob": 0, "actors": 0,
                             "rate": 0, "burst": 0}
         out["scatter"] = dict(self._scatter_counters)
+        out["dead_letters"] = (self._dlq.read() if self._dlq is not None  # (one host read of the control line)
+                               else {"entries": 0, "appended": 0, "unread": 0, "dropped": 0, "sends": 0, "torn": 0,
+                                     "redrives": 0, "redriven": 0})
         return out
 
     def close(self) -> None:
