@@ -18,7 +18,16 @@ def main():
     try:
         print(f"client: services {c.Registry.Services(C.background())}", flush=True)
         time.sleep(0.5)  # the server's listener comes up after its member
-        client = c.NewClient("calculator", None)
+        # (a GPU server registers at Join and listens once its device methods are bound: dial until it does)
+        deadline = time.monotonic() + 30.0
+        while True:
+            try:
+                client = c.NewClient("calculator", None)
+                break
+            except C.UnavailableError:
+                if time.monotonic() > deadline:
+                    raise
+                time.sleep(0.2)
         try:
             args = Args(7, 8)
             reply = client.Call("Calculator.Multiply", args)

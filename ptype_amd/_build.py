@@ -192,8 +192,12 @@ SANITIZERS = {
 }
 
 
-def build_native_test(sanitize: str = "thread", verbose: bool = False) -> str:
-    """Build ``tests/native/core_stress`` -- the host control plane without
+NATIVE_PROGRAMS = ("core_stress", "topics_parse")
+
+
+def build_native_test(sanitize: str = "thread", verbose: bool = False, program: str = "core_stress") -> str:
+    """Build ``tests/native/<program>`` (``core_stress``, or ``topics_parse``: the topic
+    records' parse and flatten on a hostile corpus) -- the host control plane without
     Python, under a sanitizer (the reference runs ``go test -race``).
 
     The sanitizer runtime must own the process, which a Python extension cannot
@@ -202,8 +206,10 @@ def build_native_test(sanitize: str = "thread", verbose: bool = False) -> str:
     """
     if sanitize not in SANITIZERS:
         raise ValueError(f"sanitize must be one of {sorted(SANITIZERS)}")
+    if program not in NATIVE_PROGRAMS:
+        raise ValueError(f"program must be one of {NATIVE_PROGRAMS}")
     srcs = [s for s in sorted(glob.glob(os.path.join(CSRC, "core", "*.cpp"))) if not s.endswith("bindings.cpp")]
-    srcs.append(os.path.join(ROOT, "tests", "native", "core_stress.cpp"))
+    srcs.append(os.path.join(ROOT, "tests", "native", program + ".cpp"))
     objdir = _variant_dir("native", sanitize)
     hdr_t = _newest_header(os.path.join(CSRC, "core"))
     # LLVM's sanitizer runtimes (ROCm's clang): gcc 11's libtsan lacks the
@@ -220,7 +226,7 @@ def build_native_test(sanitize: str = "thread", verbose: bool = False) -> str:
         if not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_t):
             jobs.append([cxx] + flags + ["-c", s, "-o", o])
     _compile_all(jobs, 8)
-    target = os.path.join(objdir, "core_stress")
+    target = os.path.join(objdir, program)
     if jobs or not os.path.exists(target) or os.path.getmtime(target) < max(os.path.getmtime(o) for o in objs):
         _run([cxx, "-pthread", "-o", target] + objs + SANITIZERS[sanitize])
     if verbose:
@@ -243,6 +249,6 @@ if __name__ == "__main__":
     elif what == "hip":
         build_hip(True)
     elif what.startswith("native-"):
-        build_native_test(what.split("-", 1)[1], True)
+        build_native_test(what.split("-", 1)[1], True, sys.argv[2] if len(sys.argv) > 2 else "core_stress")
     else:
         build_all(True)

@@ -15,6 +15,7 @@ cluster/store.go, cluster/store_config.go, cluster/rpc.go.
 from __future__ import annotations
 
 import inspect
+import json
 from typing import Any, Callable, Iterable
 
 from . import _core
@@ -188,6 +189,7 @@ class Client:
         self._router = None  # replica routing of Send (parallel/replicas.py), when the service is replicated
         self._router_checked = False
         self._tag = None  # FNV-1a64 of the service name: what this client's dead letters are filed under
+        self._topic_leases: dict = {}  # (topic, name) -> the kept-alive lease of an ephemeral subscription
 
     def _replica_router(self):
         if not self._router_checked:
@@ -397,6 +399,100 @@ class Client:
         return self._rt.ask(self.service, questions, scatter, op=op, sentinel=sentinel, router=self._replica_router(),
                             **kw)
 
+    # ------------------------------------------------------------------ publish / subscribe
+    def _topics(self):
+        if self._rt is None:
+            raise RuntimeError("topics need the cluster's device runtime (Join with a gpu: section)")
+        return self._rt.topics(self.service)
+
+    def _topic_name(self, name) -> str:
+        name = self._rt._node if name is None else str(name)
+        if not name or "/" in name:
+            raise ValueError("a subscription's name is a non-empty string without '/'")
+        return name
+
+    def Subscribe(self, topic: int, actors=None, segments=None, name: str | None = None,
+                  ephemeral: bool = False) -> int:
+        """Subscribe actors of this service to ``topic`` (an int in ``[0, gpu.topics)``): the
+        record ``store/_ptype/topics/<service>/<topic>/<name>`` (ops/topics.py has the schema)
+        is put in the replicated store, so every client of the cluster sees it.  Exactly one
+        of ``actors`` (ids: sorted, de-duplicated and cut into strided segments by
+        ``ops.topics.segments_of``) and ``segments`` (``[[start, count, stride], ...]``, kept as
+        given) names the subscribers; ``name`` (default: the node's name) identifies the
+        subscription -- the same name replaces it.  Nothing is de-duplicated across
+        subscriptions: an actor named by two of them gets every publication twice.
+        Persistent by default (actors are re-homed when a rank fails, so a subscription
+        outlives the node that made it); ``ephemeral=True`` attaches the record to a 2 s lease
+        this client keeps alive, as the service registry does, so it lapses with its owner
+        (or at ``Unsubscribe`` / ``Close``).  Returns the store revision of the put, after
+        waiting until this process's topic table reflects it: a ``Publish`` issued after
+        ``Subscribe`` returned sees the subscription; another process sees it once its own
+        table caught up (a watch event; at the latest its next re-list, 0.5 s)."""
+        from .ops import topics as T
+
+        if (actors is None) == (segments is None):
+            raise ValueError("Subscribe: exactly one of actors= and segments=")
+        table = self._topics()
+        topic = int(topic)
+        if not 0 <= topic < table.max_topics:
+            raise ValueError(f"Subscribe: topic must be in [0, {table.max_topics}) (gpu.topics)")
+        name = self._topic_name(name)
+        segs = T.check_segments(T.segments_of(actors) if segments is None else segments)
+        key, value = T.topic_key(self.service, topic, name), json.dumps({"segments": segs})
+        kv = self._rt._kv
+        old = self._topic_leases.pop((topic, name), None)
+        if old is not None:
+            old.close()
+        if ephemeral:
+            lease = _core.ShardLease(kv, key, value, T.LEASE_TTL_S)
+            self._topic_leases[(topic, name)] = lease
+            found = kv.get(key).kvs
+            rev = int(found[0].mod_revision) if found else 0
+        else:
+            rev = int(kv.put(key, value.encode()))
+        table.wait(rev)
+        return rev
+
+    def Unsubscribe(self, topic: int, name: str | None = None) -> int:
+        """Delete the subscription ``name`` (default: the node's) of ``topic`` and close its
+        lease if it was ephemeral.  Returns the store revision, after this process's topic
+        table reflects it; a subscription that does not exist is not an error."""
+        from .ops import topics as T
+
+        table = self._topics()
+        topic, name = int(topic), self._topic_name(name)
+        lease = self._topic_leases.pop((topic, name), None)
+        if lease is not None:
+            lease.close()  # (revokes: the store deletes the record)
+        _, rev = self._rt._kv.delete_rev(T.topic_key(self.service, topic, name))
+        table.wait(int(rev))
+        return int(rev)
+
+    def Topics(self) -> dict:
+        """The subscriptions this process's topic table holds, after applying what is pending:
+        ``{topic: [(name, [[start, count, stride], ...])]}``, names in key order."""
+        table = self._topics()
+        table.apply()
+        return table.view()
+
+    def Publish(self, publications, op: str = "sum", sentinel=None, **kw):
+        """Publish to topics: publication q of the ``MsgBatch`` -- its ``actor`` column names the
+        topic, ``a0`` .. ``a2`` and the method are the payload -- becomes one call to every
+        subscriber of the topic (``DistributedPubSub``'s ``Publish``, protoactor's cluster
+        pub/sub), expanded on the device from strided segments without a per-subscriber table,
+        sent with every keyword ``Send`` takes and folded per publication with ``op``, exactly
+        as ``Ask`` does.  Returns an ``ops.scatter.Answer``: ``count[q]`` subscribers addressed,
+        ``n_ok[q]`` deliveries that answered OK, ``value[q]`` the fold.  A topic outside ``[0,
+        gpu.topics)`` addresses nobody and is counted in ``oob``; one without subscribers
+        addresses nobody.  Refused under graph capture, like ``Ask``;
+        ``Stats()["runtime"]["topics"]`` has the table's and the publishes' counters."""
+        if self._rt is None:
+            raise RuntimeError("Client.Publish needs the cluster's device runtime (Join with a gpu: section)")
+        if kw.get("dead_letter") is not False:
+            kw.setdefault("dead_letter_tag", self._dead_letter_tag())
+        return self._rt.publish(self.service, publications, op=op, sentinel=sentinel, router=self._replica_router(),
+                                **kw)
+
     def Flush(self) -> None:
         """Every earlier ``Send``'s replies final (pending re-sends run now)."""
         if self._rt is not None:
@@ -410,6 +506,9 @@ class Client:
         return self._rt.tell(batch, **kw)
 
     def Close(self) -> None:
+        for lease in self._topic_leases.values():
+            lease.close()
+        self._topic_leases.clear()
         if self._router is not None:
             self._router.close()
         self._c.close()
@@ -419,6 +518,7 @@ class Client:
 
     call, go, send, tell, close, flush, ask = Call, Go, Send, Tell, Close, Flush, Ask
     dead_letters, redrive = DeadLetters, Redrive
+    subscribe, unsubscribe, topics, publish = Subscribe, Unsubscribe, Topics, Publish
 
     @property
     def conns_updated(self) -> IntChannel:

@@ -11,6 +11,7 @@
 #include "api.hpp"
 #include "dataplane.hpp"
 #include "follower.hpp"
+#include "topic_follower.hpp"
 #include "gob.hpp"
 #include "json.hpp"
 #include "records.hpp"
@@ -348,6 +349,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("dead_letters", &GpuConfig::dead_letters)
       .def_readwrite("dead_letter_entries", &GpuConfig::dead_letter_entries)
       .def_readwrite("dead_letter_mask", &GpuConfig::dead_letter_mask)
+      .def_readwrite("topics", &GpuConfig::topics)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)
       .def_readwrite("comm", &GpuConfig::comm)
@@ -506,6 +508,15 @@ PYBIND11_MODULE(_core, m) {
           },
           py::arg("key"), py::arg("end") = "")
       .def(
+          "delete_rev",
+          [](KvClient& c, const std::string& k, const std::string& end) {
+            py::gil_scoped_release nogil;
+            int64_t d = 0;
+            const int64_t rev = c.del(k, end, &d);
+            return std::make_pair(d, rev);
+          },
+          py::arg("key"), py::arg("end") = "", "delete: (keys deleted, the store revision after it)")
+      .def(
           "grant",
           [](KvClient& c, int64_t ttl) {
             py::gil_scoped_release nogil;
@@ -595,6 +606,82 @@ PYBIND11_MODULE(_core, m) {
       .def("close", &ShardLease::close, py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("record", &ShardLease::record)
       .def_property_readonly("lease", &ShardLease::lease);
+
+  // the pub/sub topic table's compiled control side (topic_follower.hpp)
+  auto topic_flat = [](const TopicFlat& t) {
+    auto arr64 = [](const std::vector<int64_t>& v) {
+      py::array_t<int64_t> a((py::ssize_t)v.size());
+      std::copy(v.begin(), v.end(), a.mutable_data());
+      return a;
+    };
+    auto arr32 = [](const std::vector<int32_t>& v) {
+      py::array_t<int32_t> a((py::ssize_t)v.size());
+      std::copy(v.begin(), v.end(), a.mutable_data());
+      return a;
+    };
+    py::list subs;
+    for (const TopicSub& s : t.subs) subs.append(py::make_tuple(s.topic, s.name, s.seg, s.n_segs));
+    py::dict d;
+    d["seg_off"] = arr64(t.seg_off);
+    d["row_off"] = arr64(t.row_off);
+    d["seg_start"] = arr32(t.seg_start);
+    d["seg_stride"] = arr32(t.seg_stride);
+    d["subs"] = subs;
+    d["records"] = t.records;
+    d["bad_records"] = t.bad_records;
+    d["topics"] = t.topics;
+    d["segments"] = t.segments();
+    d["subscribers"] = t.subscribers();
+    return d;
+  };
+  m.def(
+      "topics_flatten",
+      [topic_flat](const std::map<std::string, std::string>& records, int64_t max_topics) {
+        return topic_flat(topics_flatten(records, max_topics));
+      },
+      py::arg("records"), py::arg("max_topics"),
+      "subscription records ({\"<topic>/<name>\": value}) flattened into the topic table's arrays; a record that "
+      "is not valid is skipped and counted in bad_records");
+  m.def("topic_limits", []() {
+    py::dict d;
+    d["max_segments_per_record"] = kTopicMaxSegmentsPerRecord;
+    d["max_actor"] = kTopicMaxActor;
+    d["max_segments"] = kTopicMaxSegments;
+    d["max_topics"] = kTopicMaxTopics;
+    return d;
+  });
+  py::class_<TopicFollower, std::shared_ptr<TopicFollower>>(m, "TopicFollower")
+      .def(py::init([](std::shared_ptr<KvClient> kv, const std::string& prefix, int64_t max_topics, double relist_s,
+                       bool watch) {
+             py::gil_scoped_release nogil;
+             return std::make_shared<TopicFollower>(std::move(kv), prefix, max_topics, relist_s, watch);
+           }),
+           py::arg("kv"), py::arg("prefix"), py::arg("max_topics"), py::arg("relist_s"), py::arg("watch") = true)
+      .def("quiet", &TopicFollower::quiet)
+      .def(
+          "take",
+          [topic_flat](TopicFollower& f) {
+            int64_t rev = 0;
+            TopicFlat t;
+            {
+              py::gil_scoped_release nogil;
+              t = f.take(&rev);
+            }
+            py::dict d = topic_flat(t);
+            d["rev"] = rev;
+            d["events"] = f.events();
+            d["relists"] = f.relists();
+            return d;
+          },
+          "the flattened table of the records as they stand: the four arrays, subs [(topic, name, first segment, "
+          "segments)], the store revision it reflects and the counters")
+      .def("wait_change", &TopicFollower::wait_change, py::arg("timeout_ms"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("rev", &TopicFollower::rev)
+      .def_property_readonly("version", &TopicFollower::version)
+      .def_property_readonly("relists", &TopicFollower::relists)
+      .def_property_readonly("events", &TopicFollower::events)
+      .def_property_readonly("max_topics", &TopicFollower::max_topics)
+      .def("close", &TopicFollower::close, py::call_guard<py::gil_scoped_release>());
 
   // ---------------------------------------------------------------- registry / store
   py::class_<Registry, std::shared_ptr<Registry>>(m, "Registry");

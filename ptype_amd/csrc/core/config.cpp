@@ -182,6 +182,11 @@ void decode_ptype(const YNode& root, Config& c) {
             fail(Errc::kConfig, "gpu.dead_letter_mask must be in [2, 2^32) with bit 0 (STATUS_OK) clear");
           c.gpu.dead_letter_mask = (uint64_t)n;
         }
+        else if (g.first == "topics") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 1 || n > (1ll << 20)) fail(Errc::kConfig, "gpu.topics must be in [1, 2^20]");
+          c.gpu.topics = (uint64_t)n;
+        }
         else if (g.first == "elastic") c.gpu.elastic = want_bool(G, g.first, g.second);
         else if (g.first == "delivery") c.gpu.delivery = want_string(G, g.first, g.second);
         else if (g.first == "comm") c.gpu.comm = want_string(G, g.first, g.second);

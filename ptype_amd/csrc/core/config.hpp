@@ -77,6 +77,7 @@ struct GpuConfig {
   bool dead_letters = false;  // Send files its failed calls in the HBM dead-letter queue by default (ops/dead_letters.py)
   uint64_t dead_letter_entries = 1 << 16;  // ring records (64 B each; a power of two in [64, 2^24])
   uint64_t dead_letter_mask = 0;  // statuses that make a dead letter, bit s = status s (0: statuses 1 to 6)
+  uint64_t topics = 1024;  // pub/sub topic ids of the service: [0, topics) (ops/topics.py; [1, 2^20])
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)
   bool form_group = false;      // form the group through the store even at world <= 1 (collectives forced)

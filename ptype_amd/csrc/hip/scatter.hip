@@ -31,6 +31,15 @@
 // dwordx4 store per lane of actor and of group, two of each int64 column (the outputs are
 // the wrapper's own buffers, 16-byte aligned at row 0).  The ragged last quad stores
 // element by element.  A quad whose four rows have one owner loads its question once.
+//
+// Topics: a row's actor comes from the strided segment of its topic that holds it, so a
+// quad also needs the last segment s with row_off[s] <= row_off[seg_off[g]] + k.  It
+// searches once per question it meets (a lane-local bisection over the topic's segments)
+// and then walks forward over segment ends: row_off is strictly increasing, every segment
+// holds a row.  A tile that lies inside one question narrows the range first, for the whole
+// block, to the segments of its first and last row with the 64-way search of the owners:
+// a giant topic of a million segments costs a tile two ballot searches and its quads a
+// bisection over at most 2048 segments.
 #include "common.hpp"
 #include "scatter.hpp"
 
@@ -51,10 +60,15 @@ struct ScatterRule {
   uint32_t n_actors, actor_base;
   int64_t first_lo;
   int has_lo;
-  // members
+  // members (topics: offsets = seg_off, G = the topics)
   const int64_t* offsets;
   const int* members;
   int64_t G, n_members;
+  // topics
+  const int64_t* row_off;
+  const int* seg_start;
+  const int* seg_stride;
+  int64_t n_segs;
 };
 
 struct ScatterQuestions {
@@ -89,6 +103,12 @@ __device__ __forceinline__ uint64_t scatter_wave_scan(uint64_t v, unsigned lane)
   return v;
 }
 
+// A segment index of the table read as one in [0, n_segs]: the launchers take the table's
+// word for its own consistency, no kernel reads outside the arrays whatever it holds.
+__device__ __forceinline__ int64_t scatter_seg_clamp(int64_t s, int64_t n_segs) {
+  return s < 0 ? 0 : s > n_segs ? n_segs : s;
+}
+
 template <int RULE>
 __global__ __launch_bounds__(kScatterThreads) void scatter_count_kernel(
     ScatterRule r, const int* __restrict__ q_actor, const int64_t* __restrict__ q_a0, int64_t Q, int* __restrict__ n,
@@ -108,12 +128,20 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_count_kernel(
       if constexpr (RULE == kScatterRanges) {
         const int64_t t = q_a0[q];
         if (t > 0) v[j] = ((uint64_t)t - 1ull) / r.step + 1ull;
-      } else {
+      } else if constexpr (RULE == kScatterMembers) {
         const int64_t g = q_actor[q];
         if (g >= 0 && g < r.G)
           v[j] = (uint64_t)(r.offsets[g + 1] - r.offsets[g]);
         else
           ++n_oob;
+      } else {  // the topic's segment range, then the rows at its two ends
+        const int64_t g = q_actor[q];
+        if (g >= 0 && g < r.G) {
+          const int64_t s0 = scatter_seg_clamp(r.offsets[g], r.n_segs), s1 = scatter_seg_clamp(r.offsets[g + 1], r.n_segs);
+          if (s1 > s0) v[j] = (uint64_t)(r.row_off[s1] - r.row_off[s0]);
+        } else {
+          ++n_oob;
+        }
       }
     }
   }
@@ -218,10 +246,36 @@ __device__ __forceinline__ int scatter_owner(const int64_t* __restrict__ first, 
 
 // What a row needs of its question.
 struct ScatterQ {
-  int64_t first, a0, a1, a2;  // ranges: a2 = t; members: a0 .. a2 the question's
-  int64_t off;                // members: offsets[g]
+  int64_t first, a0, a1, a2;  // ranges: a2 = t; members and topics: a0 .. a2 the question's
+  int64_t off;                // members: offsets[g]; topics: row_off[seg_off[g]]
+  int s0, s1;                 // topics: the topic's segments [s0, s1)
   int16_t method;
 };
+
+// The segment a topics quad stands in: its rows [lo, hi) of row_off's space and its actors.
+struct ScatterSeg {
+  int s;
+  int64_t lo, hi;
+  int start, stride;
+};
+
+__device__ __forceinline__ void scatter_seg_load(const ScatterRule& r, int s, ScatterSeg* g) {
+  g->s = s;
+  g->lo = r.row_off[s], g->hi = r.row_off[s + 1];
+  g->start = r.seg_start[s], g->stride = r.seg_stride[s];
+}
+
+// The last s in [lo, hi) with row_off[s] <= at (lo when there is none); 0 <= lo < hi <= n_segs.
+__device__ __forceinline__ int scatter_seg_find(const ScatterRule& r, int lo, int hi, int64_t at) {
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (r.row_off[mid] <= at)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
 
 template <int RULE, bool MCOL>
 __device__ __forceinline__ ScatterQ scatter_question(const ScatterRule& r, const ScatterQuestions& qs,
@@ -232,7 +286,16 @@ __device__ __forceinline__ ScatterQ scatter_question(const ScatterRule& r, const
     d.a2 = qs.a0[q];
   } else {
     const int64_t g = qs.actor[q];
-    d.off = g >= 0 && g < r.G ? r.offsets[g] : 0;
+    if constexpr (RULE == kScatterMembers) {
+      d.off = g >= 0 && g < r.G ? r.offsets[g] : 0;
+    } else {
+      const bool in = g >= 0 && g < r.G;
+      d.s0 = in ? (int)scatter_seg_clamp(r.offsets[g], r.n_segs) : 0;
+      d.s1 = in ? (int)scatter_seg_clamp(r.offsets[g + 1], r.n_segs) : 0;
+      if (d.s0 >= r.n_segs) d.s0 = (int)r.n_segs - 1;  // (a question without rows only: it owns none)
+      if (d.s1 <= d.s0) d.s1 = d.s0 + 1;
+      d.off = r.row_off[d.s0];
+    }
     d.a0 = qs.a0[q];
     d.a1 = qs.a1 ? qs.a1[q] : 0;
     d.a2 = qs.a2 ? qs.a2[q] : 0;
@@ -259,6 +322,19 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
   for (int j = 0; j < kScatterQuads; ++j) {
     const int p = (j * kScatterWaves + (int)wave) * (kWave * 4) + (int)lane * 4;
     *reinterpret_cast<int4*>(&head[p]) = make_int4(p == 0 ? q_lo : -1, -1, -1, -1);
+  }
+  // topics, a tile inside one question: the segments of its first and last row bound every quad's search
+  int ts_lo = -1, ts_hi = -1;
+  if constexpr (RULE == kScatterTopics) {
+    if (q_lo == q_hi) {  // (block-uniform)
+      const ScatterQ d = scatter_question<RULE, false>(r, qs, first, q_lo);
+      int64_t at = d.off + (row0 - d.first);
+      at = at < d.off ? d.off : at;
+      ts_lo = scatter_owner(r.row_off, d.s1, at, d.s0, lane);
+      ts_lo = ts_lo < d.s0 ? d.s0 : ts_lo;
+      ts_hi = scatter_owner(r.row_off, d.s1, at + rows - 1, ts_lo, lane);
+      ts_hi = (ts_hi < ts_lo ? ts_lo : ts_hi) + 1;
+    }
   }
   __syncthreads();
   for (int q = q_lo + 1 + (int)tid; q <= q_hi; q += kScatterThreads) {
@@ -305,12 +381,14 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
     int64_t a0[4], a1[4], a2[4];
     int16_t method[4];
     ScatterQ d{};
+    ScatterSeg sg{};
     int have = -1;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       int q = max(own[j][c], carry);
       q = q < 0 ? 0 : q >= Q ? Q - 1 : q;  // (never taken: position 0 holds q_lo <= every owner < Q)
-      if (q != have) d = scatter_question<RULE, MCOL>(r, qs, first, q), have = q;
+      const bool fresh = q != have;
+      if (fresh) d = scatter_question<RULE, MCOL>(r, qs, first, q), have = q;
       const int64_t row = row0 + p + c;
       const int64_t k = row - d.first;
       group[c] = q;
@@ -320,10 +398,19 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
         a0[c] = k == 0 && r.has_lo ? r.first_lo : k * (int64_t)r.step;
         a1[c] = (k + 1) * (int64_t)r.step;
         a2[c] = d.a2;
-      } else {
+      } else if constexpr (RULE == kScatterMembers) {
         int64_t at = d.off + k;
         at = at < 0 ? 0 : at >= r.n_members ? r.n_members - 1 : at;  // (a row past the total only)
         actor[c] = r.members[at];
+        a0[c] = d.a0, a1[c] = d.a1, a2[c] = d.a2;
+      } else {
+        const int64_t at = d.off + k;
+        if (fresh) {  // one search per question of the quad ...
+          const int lo = ts_lo >= 0 ? ts_lo : d.s0, hi = ts_lo >= 0 ? ts_hi : d.s1;
+          scatter_seg_load(r, scatter_seg_find(r, lo, hi, at), &sg);
+        }
+        while (at >= sg.hi && sg.s + 1 < d.s1) scatter_seg_load(r, sg.s + 1, &sg);  // ... then a walk over segment ends
+        actor[c] = (int)((int64_t)sg.start + (int64_t)sg.stride * (at - sg.lo));
         a0[c] = d.a0, a1[c] = d.a1, a2[c] = d.a2;
       }
     }
@@ -363,7 +450,7 @@ int64_t scatter_question_tile() { return kScatterQTile; }
 int64_t scatter_expand_tile() { return kScatterTile; }
 
 static void scatter_check_rule(int rule, int64_t Q, uintptr_t q_actor, uintptr_t q_a0, int64_t step, uintptr_t offsets,
-                               int64_t G) {
+                               int64_t G, uintptr_t row_off, int64_t n_segs) {
   if (rule < 0 || rule >= kScatterRules) throw std::invalid_argument("scatter: unknown rule");
   if (Q < 1 || Q > kScatterMaxQuestions) throw std::invalid_argument("scatter: Q must be in [1, 2^26]");
   if ((q_a0 & 7u) || (q_actor & 3u) || (offsets & 7u)) throw std::invalid_argument("scatter: misaligned column");
@@ -373,6 +460,10 @@ static void scatter_check_rule(int rule, int64_t Q, uintptr_t q_actor, uintptr_t
   } else {
     if (!q_actor || !offsets) throw std::invalid_argument("scatter: members needs the actor column and the offsets");
     if (G < 0 || G > 0x7fffffffll) throw std::invalid_argument("scatter: G must be in [0, 2^31)");
+    if (rule == kScatterTopics) {
+      if (!row_off || (row_off & 7u)) throw std::invalid_argument("scatter: topics needs an aligned row_off");
+      if (n_segs < 0 || n_segs > kScatterMaxSegments) throw std::invalid_argument("scatter: n_segs must be in [0, 2^24]");
+    }
   }
 }
 
@@ -381,8 +472,8 @@ static void scatter_check_rule(int rule, int64_t Q, uintptr_t q_actor, uintptr_t
 // The question columns: Q elements, any natural alignment.
 void launch_scatter_count(int rule, uintptr_t q_actor, uintptr_t q_a0, int64_t Q, int64_t step, uintptr_t offsets,
                           int64_t G, uintptr_t n, uintptr_t first, uintptr_t tsum, uintptr_t toob, int64_t tile_cap,
-                          uintptr_t ctr, uintptr_t stream) {
-  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G);
+                          uintptr_t ctr, uintptr_t stream, uintptr_t row_off, int64_t n_segs) {
+  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs);
   const int64_t tiles = (Q + kScatterQTile - 1) / kScatterQTile;
   if (tiles > tile_cap) throw std::invalid_argument("scatter: the tile scratch is too small for Q");
   if (!n || !first || !tsum || !toob || !ctr) throw std::invalid_argument("scatter: null output or scratch");
@@ -391,7 +482,10 @@ void launch_scatter_count(int rule, uintptr_t q_actor, uintptr_t q_a0, int64_t Q
   r.step = (uint64_t)(rule == kScatterRanges ? step : 1);
   r.offsets = (const int64_t*)offsets;
   r.G = G;
-  auto kernel = rule == kScatterRanges ? scatter_count_kernel<kScatterRanges> : scatter_count_kernel<kScatterMembers>;
+  r.row_off = (const int64_t*)row_off, r.n_segs = n_segs;
+  auto kernel = rule == kScatterRanges    ? scatter_count_kernel<kScatterRanges>
+                : rule == kScatterMembers ? scatter_count_kernel<kScatterMembers>
+                                          : scatter_count_kernel<kScatterTopics>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kScatterThreads), 0, as_stream(stream), r,
                      (const int*)q_actor, (const int64_t*)q_a0, Q, (int*)n, (unsigned long long*)first,
                      (unsigned long long*)tsum, (unsigned long long*)toob);
@@ -409,15 +503,18 @@ using ScatterExpandKernel = void (*)(ScatterRule, ScatterQuestions, const int64_
 
 // The expand pass over what launch_scatter_count left in `first` and `n`; `total` is the
 // counter the host read (1 <= total <= capacity, the rows the outputs hold).  Outputs:
-// actor / group int32, a0 (a1, a2: ranges always, members when the question has them) int64,
-// method int16 when the questions carry a method column; all 16-byte aligned (method 8).
+// actor / group int32, a0 (a1, a2: ranges always, members and topics when the question has them)
+// int64, method int16 when the questions carry a method column; all 16-byte aligned (method 8).
+// Topics: offsets = seg_off int64[G + 1], row_off int64[n_segs + 1], seg_start / seg_stride
+// int32[n_segs], 1 <= n_segs <= 2^24.
 void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_t q_a1, uintptr_t q_a2, uintptr_t q_method,
                            int64_t Q, int64_t step, int64_t n_actors, int64_t actor_base, bool has_lo, int64_t first_lo,
                            uintptr_t offsets, uintptr_t members, int64_t G, int64_t n_members, uintptr_t first,
                            uintptr_t n, int64_t total, int64_t capacity, uintptr_t out_actor, uintptr_t out_a0,
                            uintptr_t out_a1, uintptr_t out_a2, uintptr_t out_method, uintptr_t out_group,
-                           uintptr_t stream) {
-  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G);
+                           uintptr_t stream, uintptr_t row_off, uintptr_t seg_start, uintptr_t seg_stride,
+                           int64_t n_segs) {
+  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs);
   if (capacity < 1 || capacity > kScatterMaxRows) throw std::invalid_argument("scatter: capacity must be in [1, 2^31 - 2]");
   if (total < 1 || total > capacity) throw std::invalid_argument("scatter: total must be in [1, capacity]");
   if (!first || !n || !out_actor || !out_a0 || !out_group) throw std::invalid_argument("scatter: null output");
@@ -435,12 +532,19 @@ void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_
     r.n_actors = (uint32_t)n_actors, r.actor_base = (uint32_t)actor_base;
     r.first_lo = first_lo, r.has_lo = has_lo ? 1 : 0;
   } else {
-    if (!members || n_members < 1 || n_members > kScatterMaxRows)
-      throw std::invalid_argument("scatter: members needs a non-empty member list");
     if ((q_a1 != 0) != (out_a1 != 0) || (q_a2 != 0) != (out_a2 != 0))
-      throw std::invalid_argument("scatter: members copies the columns the questions have");
-    r.offsets = (const int64_t*)offsets, r.members = (const int*)members;
-    r.G = G, r.n_members = n_members;
+      throw std::invalid_argument("scatter: members and topics copy the columns the questions have");
+    r.offsets = (const int64_t*)offsets, r.G = G;
+    if (rule == kScatterMembers) {
+      if (!members || n_members < 1 || n_members > kScatterMaxRows)
+        throw std::invalid_argument("scatter: members needs a non-empty member list");
+      r.members = (const int*)members, r.n_members = n_members;
+    } else {
+      if (!seg_start || !seg_stride || n_segs < 1) throw std::invalid_argument("scatter: topics needs a non-empty segment table");
+      if ((seg_start | seg_stride) & 3u) throw std::invalid_argument("scatter: misaligned segment table");
+      r.row_off = (const int64_t*)row_off, r.seg_start = (const int*)seg_start, r.seg_stride = (const int*)seg_stride;
+      r.n_segs = n_segs;
+    }
   }
   const ScatterQuestions qs{(const int*)q_actor, (const int64_t*)q_a0, (const int64_t*)q_a1, (const int64_t*)q_a2,
                             (const int16_t*)q_method};
@@ -449,8 +553,10 @@ void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_
   ScatterExpandKernel kernel;
   if (rule == kScatterRanges)
     kernel = q_method ? scatter_expand_kernel<kScatterRanges, true> : scatter_expand_kernel<kScatterRanges, false>;
-  else
+  else if (rule == kScatterMembers)
     kernel = q_method ? scatter_expand_kernel<kScatterMembers, true> : scatter_expand_kernel<kScatterMembers, false>;
+  else
+    kernel = q_method ? scatter_expand_kernel<kScatterTopics, true> : scatter_expand_kernel<kScatterTopics, false>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)((total + kScatterTile - 1) / kScatterTile)), dim3(kScatterThreads), 0,
                      as_stream(stream), r, qs, (const int64_t*)first, (const int*)n, (int)Q, total, out);
   PT_HIP_CHECK(hipGetLastError());

@@ -10,6 +10,14 @@
 //   members  g = actor[q] names a group of the CSR (offsets int64[G + 1], members
 //            int32[offsets[G]]); n = offsets[g + 1] - offsets[g], 0 for g outside [0, G)
 //            (counted in `oob`); actor = members[offsets[g] + k], a0 / a1 / a2 the question's
+//   topics   g = actor[q] names a topic of a segment table (ops/topics.py): topic g owns the
+//            segments seg_off[g] .. seg_off[g + 1] - 1 (seg_off int64[G + 1]); segment s is the
+//            actors seg_start[s] + seg_stride[s] * j, 0 <= j < row_off[s + 1] - row_off[s]
+//            (row_off int64[S + 1], the exclusive prefix of the segment counts, every count
+//            >= 1; seg_start / seg_stride int32[S]).  n = row_off[seg_off[g + 1]] -
+//            row_off[seg_off[g]], 0 for g outside [0, G) (counted in `oob`); row k belongs to
+//            the segment s of g with row_off[s] <= row_off[seg_off[g]] + k < row_off[s + 1];
+//            a0 / a1 / a2 the question's.  No per-subscriber table exists.
 // The method is the question's (one id, or an int16 column copied per row); `group`
 // holds the question index of every row.
 //
@@ -22,12 +30,15 @@ namespace ptype {
 
 constexpr int kScatterRanges = 0;
 constexpr int kScatterMembers = 1;
-constexpr int kScatterRules = 2;
+constexpr int kScatterTopics = 2;
+constexpr int kScatterRules = 3;
 
 constexpr int kScatterCtrWords = 2;
 // rows of one expansion: a Gather takes M < 2^31 - 1 replies
 constexpr int64_t kScatterMaxRows = 0x7ffffffell;
 constexpr int64_t kScatterMaxQuestions = 1ll << 26;
 constexpr int64_t kScatterMaxStep = 0x7fffffffll;
+// segments of one topic table: a segment index fits the int of the owner search
+constexpr int64_t kScatterMaxSegments = 1ll << 24;
 
 }  // namespace ptype

@@ -5,7 +5,7 @@ The scatter half of the reference's scatter-gather (``splitWork``, coordinator.g
 that turns question q of a short ``MsgBatch`` into ``n[q] >= 0`` calls.  ``first[q]`` is
 the exclusive prefix of ``n``: question q owns the rows ``first[q] .. first[q] + n[q] - 1``
 of the expanded batch, in question order, and ``group[row] = q``.  With ``k = row -
-first[q]`` the two rules are
+first[q]`` the three rules are
 
 ``Scatter.ranges(step, n_actors, first_lo=None, actor_base=0)`` -- ``splitWork`` for any
 step.  ``t = a0[q]``; ``n[q] = 0`` for ``t <= 0``, else ``(t - 1) // step + 1`` (unsigned:
@@ -21,6 +21,18 @@ the group ``g`` and ``n[q] = offsets[g + 1] - offsets[g]``.  A group id outside 
 gives ``n[q] = 0`` and is counted in ``oob``.  A row gets ``actor = members[offsets[g] +
 k]`` and the question's own ``a0``, ``a1``, ``a2``.  Keeping the CSR in step with a store is
 the caller's business; ``set_members`` replaces it.
+
+``Scatter.topics(table)`` -- one call to every subscriber of a topic, from strided segments
+(``ops/topics.py``: a ``TopicTable`` that follows the subscriptions kept in the replicated
+store; no per-subscriber list exists anywhere).  The table is four arrays: ``seg_off``
+int64[G + 1] (topic ``g`` owns the segments ``seg_off[g] .. seg_off[g + 1] - 1``), ``row_off``
+int64[S + 1] (the exclusive prefix of the segment counts, every count >= 1), ``seg_start`` and
+``seg_stride`` int32[S].  The question's ``actor`` column names the topic ``g``; ``n[q] =
+row_off[seg_off[g + 1]] - row_off[seg_off[g]]``, 0 for ``g`` outside ``[0, G)`` (counted in
+``oob``; a topic without a subscriber gives 0 and is not out of range).  Row ``k`` belongs to
+the segment ``s`` of ``g`` with ``row_off[s] <= row_off[seg_off[g]] + k < row_off[s + 1]`` and
+gets ``actor = seg_start[s] + seg_stride[s] * (row_off[seg_off[g]] + k - row_off[s])`` and
+the question's own ``a0``, ``a1``, ``a2``.  Every expand reads the table as it then stands.
 
 Either way the method is the question's: one id, or an int16 column copied per row.
 
@@ -47,12 +59,13 @@ from . import _ptr, hip, raw_stream
 from .batch import MsgBatch
 from .gather import Gather
 
-RULES = ("ranges", "members")   # scatter.hpp kScatterRanges, kScatterMembers
+RULES = ("ranges", "members", "topics")  # scatter.hpp kScatterRanges, kScatterMembers, kScatterTopics
 QUESTION_TILE = 1024            # scatter.hip kScatterQTile
 TILE = 2048                     # scatter.hip kScatterTile
 MAX_ROWS = (1 << 31) - 2        # scatter.hpp kScatterMaxRows
 MAX_QUESTIONS = 1 << 26         # scatter.hpp kScatterMaxQuestions
 MAX_STEP = (1 << 31) - 1        # scatter.hpp kScatterMaxStep
+MAX_SEGMENTS = 1 << 24          # scatter.hpp kScatterMaxSegments
 U64_MAX = (1 << 64) - 1
 I32_MAX = (1 << 31) - 1
 
@@ -70,6 +83,14 @@ def scatter_counts(rule: "Scatter", questions: MsgBatch):
         n = np.zeros(t.size, dtype=np.uint64)
         n[pos] = (t[pos].astype(np.uint64) - np.uint64(1)) // np.uint64(rule.step) + np.uint64(1)
         oob = 0
+    elif rule.rule == "topics":
+        t = rule.table.host
+        g = _np(questions.actor, np.int64)
+        inside = (g >= 0) & (g < t["seg_off"].size - 1)
+        gi = np.where(inside, g, 0)
+        rows = t["row_off"][t["seg_off"][gi + 1]] - t["row_off"][t["seg_off"][gi]]
+        n = np.where(inside, rows, 0).astype(np.uint64)
+        oob = int((~inside).sum())
     else:
         g = _np(questions.actor, np.int64)
         inside = (g >= 0) & (g < rule.G)
@@ -82,7 +103,7 @@ def scatter_counts(rule: "Scatter", questions: MsgBatch):
 
 
 def scatter_ref(rule: "Scatter", questions: MsgBatch) -> dict:
-    """The spec in numpy: ``{"actor" int32[T], "a0" / "a1" / "a2" int64[T] (members: None
+    """The spec in numpy: ``{"actor" int32[T], "a0" / "a1" / "a2" int64[T] (members, topics: None
     where the questions have none), "method" (the id, or int16[T]), "group" int32[T],
     "first" int64[Q], "n" int32[Q], "total", "oob"}`` as CPU tensors and Python ints."""
     n64, total, oob = scatter_counts(rule, questions)
@@ -103,7 +124,15 @@ def scatter_ref(rule: "Scatter", questions: MsgBatch) -> dict:
         a2 = _np(questions.a0, np.int64)[group]
     else:
         g = _np(questions.actor, np.int64)[group]
-        actor = rule.members_host[rule.offsets_host[g] + k] if total else np.zeros(0, dtype=np.int64)
+        if not total:
+            actor = np.zeros(0, dtype=np.int64)
+        elif rule.rule == "members":
+            actor = rule.members_host[rule.offsets_host[g] + k]
+        else:
+            t = rule.table.host
+            at = t["row_off"][t["seg_off"][g]] + k
+            seg = np.searchsorted(t["row_off"], at, side="right") - 1  # (row_off is strictly increasing)
+            actor = t["seg_start"][seg].astype(np.int64) + t["seg_stride"][seg].astype(np.int64) * (at - t["row_off"][seg])
         a0 = _np(questions.a0, np.int64)[group]
         a1 = None if questions.a1 is None else _np(questions.a1, np.int64)[group]
         a2 = None if questions.a2 is None else _np(questions.a2, np.int64)[group]
@@ -164,7 +193,7 @@ class Answer:
 
 class Scatter:
     """A scatter rule with its output buffers (module docstring).  Build one with
-    ``Scatter.ranges`` or ``Scatter.members``."""
+    ``Scatter.ranges``, ``Scatter.members`` or ``Scatter.topics``."""
 
     def __init__(self, rule: str, capacity: int, q_capacity: int | None):
         if rule not in RULES:
@@ -182,8 +211,10 @@ class Scatter:
         self.step, self.n_actors, self.first_lo, self.actor_base = 1, 1, None, 0
         # members
         self.G, self.offsets, self.members_, self.offsets_host, self.members_host = 0, None, None, None, None
+        # topics
+        self.table = None
 
-    # ------------------------------------------------------------------ the two rules
+    # ------------------------------------------------------------------ the three rules
     @classmethod
     def ranges(cls, step: int, n_actors: int, first_lo: int | None = None, actor_base: int = 0,
                capacity: int = 1 << 20, q_capacity: int | None = None) -> "Scatter":
@@ -206,6 +237,21 @@ class Scatter:
         s = cls("members", capacity, q_capacity)
         s.set_members(offsets, members)
         return s
+
+    @classmethod
+    def topics(cls, table, capacity: int = 1 << 20, q_capacity: int | None = None) -> "Scatter":
+        """``table``: an ``ops.topics.TopicTable`` (or anything with its ``host`` dict of numpy
+        arrays, ``device_arrays(device)`` and ``max_topics``); ``set_table`` replaces it."""
+        s = cls("topics", capacity, q_capacity)
+        s.set_table(table)
+        return s
+
+    def set_table(self, table) -> None:
+        if self.rule != "topics":
+            raise ValueError("Scatter.set_table: not a topics rule")
+        if not hasattr(table, "host") or not hasattr(table, "device_arrays"):
+            raise ValueError("Scatter.topics: the table is an ops.topics.TopicTable")
+        self.table = table
 
     def set_members(self, offsets: torch.Tensor, members: torch.Tensor) -> None:
         """Replace the group table (validated here, once: one host read of the CSR)."""
@@ -281,7 +327,7 @@ class Scatter:
         elif dev != self.device:
             raise ValueError("Scatter.expand: the questions live on another device than the buffers")
         mcol = not isinstance(questions.method, int)
-        members = self.rule == "members"
+        members = self.rule != "ranges"  # (members and topics copy the question's columns)
         has1 = not members or questions.a1 is not None
         has2 = not members or questions.a2 is not None
         if dev.type != "cuda":
@@ -318,6 +364,12 @@ class Scatter:
     def _count(self, cols, Q: int) -> None:
         """The count, scan and first launches over the question columns ``cols`` (actor, a0,
         a1, a2, method; contiguous or None): ``n``, ``first`` and ``ctr`` on the device."""
+        if self.rule == "topics":
+            seg_off, G, row_off, n_segs, _, _ = self.table.launch_args(self.device)
+            hip().scatter_count(2, _ptr(cols[0]), _ptr(cols[1]), Q, 1, seg_off, G, _ptr(self.n), _ptr(self.first),
+                                _ptr(self.tsum), _ptr(self.toob), self.tile_cap, _ptr(self.ctr), raw_stream(self.device),
+                                row_off, n_segs)
+            return
         hip().scatter_count(RULES.index(self.rule), _ptr(cols[0]), _ptr(cols[1]), Q, self.step, _ptr(self.offsets),
                             self.G, _ptr(self.n), _ptr(self.first), _ptr(self.tsum), _ptr(self.toob), self.tile_cap,
                             _ptr(self.ctr), raw_stream(self.device))
@@ -325,8 +377,16 @@ class Scatter:
     def _fill(self, cols, Q: int, total: int) -> None:
         """The expand launch: ``total`` (what ``_count`` left in ``ctr[0]``, read and checked
         by the caller) rows of the batch columns and of ``group``."""
-        members = self.rule == "members"
+        members = self.rule != "ranges"
         out = (lambda buf, col: _ptr(buf) if not members or col is not None else 0)
+        if self.rule == "topics":
+            seg_off, G, row_off, n_segs, seg_start, seg_stride = self.table.launch_args(self.device)
+            hip().scatter_expand(2, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), Q, 1, 1, 0,
+                                 False, 0, seg_off, 0, G, 0, _ptr(self.first), _ptr(self.n), total, self.capacity,
+                                 _ptr(self.actor), _ptr(self.a0), out(self.a1, cols[2]), out(self.a2, cols[3]),
+                                 0 if cols[4] is None else _ptr(self.method), _ptr(self.group), raw_stream(self.device),
+                                 row_off, seg_start, seg_stride, n_segs)
+            return
         hip().scatter_expand(RULES.index(self.rule), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]),
                              _ptr(cols[4]), Q, self.step, self.n_actors, self.actor_base, self.first_lo is not None,
                              self.first_lo or 0, _ptr(self.offsets), _ptr(self.members_), self.G,

@@ -76,7 +76,7 @@ class DeviceRuntime:
                  breaker: bool = False, breaker_threshold: int = 5, breaker_cooldown: int = 8,
                  breaker_actors: int = 0, breaker_trip_on=None, limit: bool = False, limit_rate: int = 1,
                  limit_burst: int = 1, limit_actors: int = 0, dead_letters: bool = False,
-                 dead_letter_entries: int = 1 << 16, dead_letter_mask=None):
+                 dead_letter_entries: int = 1 << 16, dead_letter_mask=None, max_topics: int = 1024):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -190,6 +190,13 @@ class DeviceRuntime:
                                        max_rows=self.max_batch)
         # Scatter-gather (ask, ops/scatter.py): host counters, from what every expansion read
         self._scatter_counters = {"asks": 0, "questions": 0, "rows": 0, "oob": 0}
+        # Pub/sub topics (publish, ops/topics.py): per service the follower-fed table and its scatter,
+        # created by the first Subscribe or Publish (nothing is watched before); host counters
+        self.max_topics = int(max_topics)
+        if not 1 <= self.max_topics <= 1 << 20:
+            raise ValueError("max_topics must be in [1, 2**20]")
+        self._topics: dict = {}
+        self._topic_counters = {"publishes": 0, "publications": 0, "rows": 0, "oob": 0}
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -258,7 +265,8 @@ class DeviceRuntime:
                  breaker_threshold=g.breaker_threshold, breaker_cooldown=g.breaker_cooldown,
                  breaker_actors=g.breaker_actors, limit=g.limit, limit_rate=g.limit_rate,
                  limit_burst=g.limit_burst, limit_actors=g.limit_actors, dead_letters=g.dead_letters,
-                 dead_letter_entries=g.dead_letter_entries, dead_letter_mask=g.dead_letter_mask or None)
+                 dead_letter_entries=g.dead_letter_entries, dead_letter_mask=g.dead_letter_mask or None,
+                 max_topics=g.topics)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -747,6 +755,53 @@ class DeviceRuntime:
             return Answer(e64, e32, e32, e32, e32, exp.first, exp.n, exp.oob, out[0], out[1])
         return Answer(g.value, g.status, g.n_ok, g.count, g.bad_row, exp.first, exp.n, exp.oob, out[0], out[1])
 
+    def topics(self, service: str | None = None, table=None):
+        """The ``ops.topics.TopicTable`` of ``service`` (default: the runtime's), created with its
+        follower on first use; its scatter is ``topics(service).scatter``.  ``table``: install
+        this table instead (one that follows no store: a runtime without a control plane)."""
+        from .ops.scatter import Scatter
+        from .ops.topics import TopicTable
+
+        service = self.service if service is None else service
+        t = self._topics.get(service)
+        if table is not None:
+            if t is not None:
+                t.close()
+            t = None
+        if t is None:
+            kv = getattr(self, "_kv", None)
+            if table is None and kv is None:
+                raise RuntimeError("topics need the cluster's control plane: this runtime is not attached to a store "
+                                   "(Join with a gpu: section, or DeviceRuntime.attach)")
+            ex = self.exchange
+            t = table if table is not None else TopicTable(self.device, self.max_topics, kv=kv, service=service)
+            t.scatter = Scatter.topics(t, capacity=ex.max_chunk * ex.chunks)
+            self._topics[service] = t
+        return t
+
+    def publish(self, service: str | None, publications: B.MsgBatch, op: str = "sum", sentinel=None, **send_kw):
+        """Publish/subscribe in one call (Akka's ``DistributedPubSub`` ``Publish``): publication
+        q -- its ``actor`` column names a topic -- becomes one call to every subscriber of the
+        topic, expanded on the device from the store's subscriptions (``ops/topics.py``), sent,
+        and folded per publication.  ``topics(service).apply()`` followed by ``ask`` with the
+        table's scatter: everything ``ask`` documents holds unchanged (the Send keywords, the
+        refusal under capture, each rank expanding its own publications, no new collective).
+        A subscription is visible to a Publish once ``TopicTable.wait`` of its revision returned
+        (``Client.Subscribe`` waits for its own)."""
+        t = self._topics.get(self.service if service is None else service) or self.topics(service)
+        if self._exchange is not None and self._exchange._capturing:
+            raise ValueError("publish inside a captured Send: the total of the expansion is read on the host")
+        t.apply()
+        a = self._scatter_counters
+        questions, rows, oob = a["questions"], a["rows"], a["oob"]
+        out = self.ask(service, publications, t.scatter, op=op, sentinel=sentinel, **send_kw)
+        c = self._topic_counters
+        c["publishes"] += 1
+        c["publications"] += a["questions"] - questions
+        c["rows"] += a["rows"] - rows
+        c["oob"] += a["oob"] - oob
+        return out
+
     def cache_clear(self) -> None:
         """Drop every entry of the reply cache (O(1): the cache's epoch moves on)."""
         if self._cache is not None:
@@ -1223,6 +1278,10 @@ class DeviceRuntime:
             out["limit"] = {"sends": 0, "messages": 0, "rejected": 0, "sent": 0, "throttled": 0, "oob": 0, "actors": 0,
                             "rate": 0, "burst": 0}
         out["scatter"] = dict(self._scatter_counters)
+        t = self._topics.get(self.service)
+        out["topics"] = dict(t.stats() if t is not None else {"topics": 0, "segments": 0, "subscribers": 0, "records": 0,
+                                                              "bad_records": 0, "applied_rev": 0},
+                             **self._topic_counters)
         out["dead_letters"] = (self._dlq.read() if self._dlq is not None  # (one host read of the control line)
                                else {"entries": 0, "appended": 0, "unread": 0, "dropped": 0, "sends": 0, "torn": 0,
                                      "redrives": 0, "redriven": 0})
@@ -1241,6 +1300,8 @@ class DeviceRuntime:
                 _log.warning("close: deferred re-sends not resolved: %s", str(e)[:300])
         for lease in getattr(self, "_replica_leases", {}).values():
             lease.close()
+        for t in self._topics.values():
+            t.close()
         if self.mirror is not None:
             self.mirror.close()
         if self.shard_lease is not None:
