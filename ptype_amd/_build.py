@@ -192,12 +192,12 @@ SANITIZERS = {
 }
 
 
-NATIVE_PROGRAMS = ("core_stress", "topics_parse")
+NATIVE_PROGRAMS = ("core_stress", "topics_parse", "queues_parse")
 
 
 def build_native_test(sanitize: str = "thread", verbose: bool = False, program: str = "core_stress") -> str:
-    """Build ``tests/native/<program>`` (``core_stress``, or ``topics_parse``: the topic
-    records' parse and flatten on a hostile corpus) -- the host control plane without
+    """Build ``tests/native/<program>`` (``core_stress``, or ``topics_parse`` / ``queues_parse``:
+    the topic records' parse and flatten on hostile corpora) -- the host control plane without
     Python, under a sanitizer (the reference runs ``go test -race``).
 
     The sanitizer runtime must own the process, which a Python extension cannot

@@ -412,7 +412,7 @@ class Client:
         return name
 
     def Subscribe(self, topic: int, actors=None, segments=None, name: str | None = None,
-                  ephemeral: bool = False) -> int:
+                  ephemeral: bool = False, queue: bool = False) -> int:
         """Subscribe actors of this service to ``topic`` (an int in ``[0, gpu.topics)``): the
         record ``store/_ptype/topics/<service>/<topic>/<name>`` (ops/topics.py has the schema)
         is put in the replicated store, so every client of the cluster sees it.  Exactly one
@@ -427,7 +427,14 @@ class Client:
         (or at ``Unsubscribe`` / ``Close``).  Returns the store revision of the put, after
         waiting until this process's topic table reflects it: a ``Publish`` issued after
         ``Subscribe`` returned sees the subscription; another process sees it once its own
-        table caught up (a watch event; at the latest its next re-list, 0.5 s)."""
+        table caught up (a watch event; at the latest its next re-list, 0.5 s).
+
+        ``queue=True`` makes it a **queue subscription** (competing consumers: Akka's
+        ``sendOneMessageToEachGroup``, a NATS queue group, a Kafka consumer group): a publication
+        to the topic reaches exactly ONE of the subscription's members -- the ids of its segments
+        in order, at most ``2**31 - 1`` of them -- instead of all of them: a pool of workers
+        behind a topic.  ``Publish`` picks the member (``key=``, ``by=``).  Re-subscribing under
+        the same name replaces the subscription, whichever kind it was."""
         from .ops import topics as T
 
         if (actors is None) == (segments is None):
@@ -438,7 +445,12 @@ class Client:
             raise ValueError(f"Subscribe: topic must be in [0, {table.max_topics}) (gpu.topics)")
         name = self._topic_name(name)
         segs = T.check_segments(T.segments_of(actors) if segments is None else segments)
-        key, value = T.topic_key(self.service, topic, name), json.dumps({"segments": segs})
+        if not isinstance(queue, bool):
+            raise ValueError("Subscribe: queue is True or False")
+        if queue and sum(s[1] for s in segs) > T.MAX_QUEUE_MEMBERS:
+            raise ValueError(f"Subscribe: a queue subscription holds at most {T.MAX_QUEUE_MEMBERS} members")
+        record = {"segments": segs, "queue": True} if queue else {"segments": segs}
+        key, value = T.topic_key(self.service, topic, name), json.dumps(record)
         kv = self._rt._kv
         old = self._topic_leases.pop((topic, name), None)
         if old is not None:
@@ -468,14 +480,16 @@ class Client:
         table.wait(int(rev))
         return int(rev)
 
-    def Topics(self) -> dict:
-        """The subscriptions this process's topic table holds, after applying what is pending:
-        ``{topic: [(name, [[start, count, stride], ...])]}``, names in key order."""
+    def Topics(self, queues: bool = False) -> dict:
+        """The ordinary subscriptions this process's topic table holds, after applying what is
+        pending: ``{topic: [(name, [[start, count, stride], ...])]}``, names in key order.
+        ``queues=True``: every subscription as ``(name, segments, queue)``, a topic's ordinary
+        ones (``queue`` False) before its queue subscriptions (True)."""
         table = self._topics()
         table.apply()
-        return table.view()
+        return table.view(queues=True) if queues else table.view()
 
-    def Publish(self, publications, op: str = "sum", sentinel=None, **kw):
+    def Publish(self, publications, op: str = "sum", sentinel=None, key=None, by=None, **kw):
         """Publish to topics: publication q of the ``MsgBatch`` -- its ``actor`` column names the
         topic, ``a0`` .. ``a2`` and the method are the payload -- becomes one call to every
         subscriber of the topic (``DistributedPubSub``'s ``Publish``, protoactor's cluster
@@ -485,13 +499,23 @@ class Client:
         ``n_ok[q]`` deliveries that answered OK, ``value[q]`` the fold.  A topic outside ``[0,
         gpu.topics)`` addresses nobody and is counted in ``oob``; one without subscribers
         addresses nobody.  Refused under graph capture, like ``Ask``;
-        ``Stats()["runtime"]["topics"]`` has the table's and the publishes' counters."""
+        ``Stats()["runtime"]["topics"]`` has the table's and the publishes' counters.
+
+        After them a publication makes one call per **queue subscription** of its topic
+        (``Subscribe(queue=True)``), in key order, to one member: ``by="key"`` (default) picks it
+        from the hash of ``key[q]`` -- ``key`` an int64[Q] column, by default the publication's
+        ``a0`` -- so every publication of one key reaches the same member while the membership
+        stands (per-key ordering: Kafka's keyed records); ``by="index"`` walks the members round
+        robin (publication ``q`` of the batch takes ``(seq + q) mod c``; ``seq`` advances by Q).
+        ``count[q]`` is then the ordinary subscribers plus the queue subscriptions of the topic.
+        ``Stats()["runtime"]["queues"]`` counts the queue subscriptions, their members and
+        segments, and the queue rows published."""
         if self._rt is None:
             raise RuntimeError("Client.Publish needs the cluster's device runtime (Join with a gpu: section)")
         if kw.get("dead_letter") is not False:
             kw.setdefault("dead_letter_tag", self._dead_letter_tag())
-        return self._rt.publish(self.service, publications, op=op, sentinel=sentinel, router=self._replica_router(),
-                                **kw)
+        return self._rt.publish(self.service, publications, op=op, sentinel=sentinel, key=key, by=by,
+                                router=self._replica_router(), **kw)
 
     def Flush(self) -> None:
         """Every earlier ``Send``'s replies final (pending re-sends run now)."""

@@ -621,7 +621,14 @@ PYBIND11_MODULE(_core, m) {
     };
     py::list subs;
     for (const TopicSub& s : t.subs) subs.append(py::make_tuple(s.topic, s.name, s.seg, s.n_segs));
+    py::list queues;
+    for (const TopicSub& s : t.queues) queues.append(py::make_tuple(s.topic, s.name, s.seg, s.n_segs));
     py::dict d;
+    d["q_off"] = arr64(t.q_off);
+    d["q_seg"] = arr64(t.q_seg);
+    d["queues"] = queues;
+    d["queue_segments"] = t.queue_segments();
+    d["queue_members"] = t.queue_members();
     d["seg_off"] = arr64(t.seg_off);
     d["row_off"] = arr64(t.row_off);
     d["seg_start"] = arr32(t.seg_start);
@@ -641,13 +648,16 @@ PYBIND11_MODULE(_core, m) {
       },
       py::arg("records"), py::arg("max_topics"),
       "subscription records ({\"<topic>/<name>\": value}) flattened into the topic table's arrays; a record that "
-      "is not valid is skipped and counted in bad_records");
+      "is not valid is skipped and counted in bad_records.  The queue subscriptions' segments follow the ordinary ones "
+      "in row_off / seg_start / seg_stride; q_off, q_seg and queues [(topic, name, first segment, segments)] describe them");
   m.def("topic_limits", []() {
     py::dict d;
     d["max_segments_per_record"] = kTopicMaxSegmentsPerRecord;
     d["max_actor"] = kTopicMaxActor;
     d["max_segments"] = kTopicMaxSegments;
     d["max_topics"] = kTopicMaxTopics;
+    d["max_queues"] = kTopicMaxQueues;
+    d["max_queue_members"] = kTopicMaxQueueMembers;
     return d;
   });
   py::class_<TopicFollower, std::shared_ptr<TopicFollower>>(m, "TopicFollower")

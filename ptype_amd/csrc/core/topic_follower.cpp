@@ -70,7 +70,13 @@ bool shallow(const std::string& s) {
 }  // namespace
 
 bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out) {
+  bool queue = false;
+  return topic_parse_record(json, out, &queue);
+}
+
+bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out, bool* queue) {
   out->clear();
+  *queue = false;
   if (!shallow(json)) return false;
   JValue v;
   try {
@@ -82,6 +88,11 @@ bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out)
   const JValue* segs = v.get("segments");
   if (!segs || segs->kind != JValue::kArray) return false;
   if (segs->arr.empty() || (int64_t)segs->arr.size() > kTopicMaxSegmentsPerRecord) return false;
+  if (const JValue* q = v.get("queue")) {
+    if (q->kind != JValue::kBool) return false;
+    *queue = q->b;
+  }
+  int64_t members = 0;
   out->reserve(segs->arr.size());
   for (const JValue& s : segs->arr) {
     if (s.kind != JValue::kArray || s.arr.size() != 3) return false;
@@ -94,8 +105,10 @@ bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out)
         t.stride > kTopicMaxActor)
       return false;
     if (t.count > 1 && t.stride > (kTopicMaxActor - t.start) / (t.count - 1)) return false;
+    members += t.count;  // (1024 counts of at most 2^31 - 1)
     out->push_back(t);
   }
+  if (*queue && members > kTopicMaxQueueMembers) return false;
   return true;
 }
 
@@ -121,39 +134,58 @@ TopicFlat topics_flatten(const std::map<std::string, std::string>& records, int6
     int64_t topic;
     std::string name;
     std::vector<TopicSegment> segs;
+    bool queue;
   };
   std::vector<Rec> good;
-  std::vector<int64_t> per_topic((size_t)max_topics + 1, 0);  // segments of topic g at [g + 1]
-  int64_t total = 0;
+  std::vector<int64_t> per_topic((size_t)max_topics + 1, 0);   // ordinary segments of topic g at [g + 1]
+  std::vector<int64_t> q_per_topic((size_t)max_topics + 1, 0);  // queue subscriptions of topic g at [g + 1]
+  int64_t total = 0, ordinary = 0, n_queues = 0;
   for (const auto& kv : records) {
     ++t.records;
     Rec r;
-    if (!topic_parse_key(kv.first, max_topics, &r.topic, &r.name) || !topic_parse_record(kv.second, &r.segs) ||
-        total + (int64_t)r.segs.size() > kTopicMaxSegments) {
+    r.queue = false;
+    if (!topic_parse_key(kv.first, max_topics, &r.topic, &r.name) || !topic_parse_record(kv.second, &r.segs, &r.queue) ||
+        total + (int64_t)r.segs.size() > kTopicMaxSegments || (r.queue && n_queues + 1 > kTopicMaxQueues)) {
       ++t.bad_records;
       continue;
     }
     total += (int64_t)r.segs.size();
-    per_topic[(size_t)r.topic + 1] += (int64_t)r.segs.size();
+    if (r.queue) {
+      ++n_queues;
+      ++q_per_topic[(size_t)r.topic + 1];
+    } else {
+      ordinary += (int64_t)r.segs.size();
+      per_topic[(size_t)r.topic + 1] += (int64_t)r.segs.size();
+    }
     good.push_back(std::move(r));
   }
   // by topic; key order within a topic is the map's order, kept by the stable sort
   std::stable_sort(good.begin(), good.end(), [](const Rec& a, const Rec& b) { return a.topic < b.topic; });
   t.seg_off.assign((size_t)max_topics + 1, 0);
+  t.q_off.assign((size_t)max_topics + 1, 0);
   for (int64_t g = 0; g < max_topics; ++g) {
     t.seg_off[(size_t)g + 1] = t.seg_off[(size_t)g] + per_topic[(size_t)g + 1];
+    t.q_off[(size_t)g + 1] = t.q_off[(size_t)g] + q_per_topic[(size_t)g + 1];
     if (per_topic[(size_t)g + 1]) ++t.topics;
   }
   t.row_off.reserve((size_t)total + 1);
   t.seg_start.reserve((size_t)total);
   t.seg_stride.reserve((size_t)total);
+  t.q_seg.reserve((size_t)n_queues + 1);
   t.row_off.push_back(0);
-  for (Rec& r : good) {
-    t.subs.push_back(TopicSub{r.topic, std::move(r.name), (int64_t)t.seg_start.size(), (int64_t)r.segs.size()});
-    for (const TopicSegment& s : r.segs) {
-      t.seg_start.push_back((int32_t)s.start);
-      t.seg_stride.push_back((int32_t)s.stride);
-      t.row_off.push_back(t.row_off.back() + s.count);
+  // the ordinary subscriptions first, then the queue subscriptions: both by topic, then key order
+  for (const bool queue : {false, true}) {
+    if (queue) t.q_seg.push_back(ordinary);
+    for (Rec& r : good) {
+      if (r.queue != queue) continue;
+      (queue ? t.queues : t.subs)
+          .push_back(TopicSub{r.topic, std::move(r.name), (int64_t)t.seg_start.size(), (int64_t)r.segs.size()});
+      for (const TopicSegment& s : r.segs) {
+        t.seg_start.push_back((int32_t)s.start);
+        t.seg_stride.push_back((int32_t)s.stride);
+        t.row_off.push_back(t.row_off.back() + s.count);
+      }
+      if (queue) t.q_seg.push_back((int64_t)t.seg_start.size());
     }
   }
   return t;

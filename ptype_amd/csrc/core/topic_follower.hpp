@@ -3,7 +3,7 @@
 // arrays the scatter's `topics` rule reads (csrc/hip/scatter.hpp).
 //
 // Record: `store/_ptype/topics/<service>/<topic>/<name>` ->
-//   {"segments": [[start, count, stride], ...]}
+//   {"segments": [[start, count, stride], ...], "queue": true}
 // `topic` is a decimal integer in [0, max_topics), `name` the subscription's name.  Segment
 // s stands for the actor ids start + stride * k, 0 <= k < count; valid when count >= 1,
 // stride >= 1, start >= 0 and start + stride * (count - 1) <= 2^31 - 2; a record holds 1 to
@@ -11,6 +11,16 @@
 // order; nothing is de-duplicated across records.  A record that is not valid (bad JSON, a
 // field out of range, too many segments, a topic outside [0, max_topics), a table past
 // 2^24 segments) is skipped and counted, never an error.
+//
+// `queue` is optional: absent or false is an ordinary subscription (every member gets every
+// publication).  true makes the record a queue subscription -- a publication reaches exactly
+// one of its members, the ids of its segments in record order; their number lies in
+// [1, 2^31 - 1].  Any other value of `queue` makes the record invalid.  The queue segments
+// follow the ordinary ones in row_off / seg_start / seg_stride (seg_off[max_topics] keeps
+// bounding the ordinary ones); q_off maps a topic to its queue subscriptions (key order),
+// q_seg a queue subscription to its first segment.  Ordinary plus queue segments and the
+// queue subscriptions are at most 2^24 each; a record past a limit is skipped and counted.
+// For records without a queue subscription the four ordinary arrays are what they always were.
 //
 // topics_flatten() is the pure part -- records in, arrays out, no thread, no KvClient.
 // TopicFollower keeps the prefix's records current like RegistryFollower keeps the shard
@@ -39,6 +49,8 @@ constexpr int64_t kTopicMaxSegmentsPerRecord = 1024;
 constexpr int64_t kTopicMaxActor = 0x7ffffffell;      // 2^31 - 2
 constexpr int64_t kTopicMaxSegments = 1ll << 24;      // of one table (scatter.hpp kScatterMaxSegments)
 constexpr int64_t kTopicMaxTopics = 1ll << 20;        // gpu.topics
+constexpr int64_t kTopicMaxQueues = 1ll << 24;        // queue subscriptions of one table
+constexpr int64_t kTopicMaxQueueMembers = 0x7fffffffll;  // of one queue subscription: 2^31 - 1
 
 struct TopicSegment {
   int64_t start = 0, count = 0, stride = 0;
@@ -53,17 +65,27 @@ struct TopicSub {
 
 struct TopicFlat {
   std::vector<int64_t> seg_off;     // [max_topics + 1]
-  std::vector<int64_t> row_off;     // [S + 1]
+  std::vector<int64_t> row_off;     // [S + 1]: the ordinary segments, then the queue segments
   std::vector<int32_t> seg_start;   // [S]
   std::vector<int32_t> seg_stride;  // [S]
-  std::vector<TopicSub> subs;       // by topic, then key order
+  std::vector<int64_t> q_off;       // [max_topics + 1]: topic -> its queue subscriptions
+  std::vector<int64_t> q_seg;       // [NQ + 1]: queue subscription -> its first segment; q_seg[0] = segments()
+  std::vector<TopicSub> subs;       // the ordinary subscriptions: by topic, then key order
+  std::vector<TopicSub> queues;     // the queue subscriptions, likewise
   int64_t records = 0, bad_records = 0;
-  int64_t topics = 0;               // topics with a subscriber
-  int64_t subscribers() const { return row_off.empty() ? 0 : row_off.back(); }
-  int64_t segments() const { return (int64_t)seg_start.size(); }
+  int64_t topics = 0;               // topics with an ordinary subscriber
+  // of the ordinary subscriptions
+  int64_t segments() const { return seg_off.empty() ? 0 : seg_off.back(); }
+  int64_t subscribers() const { return row_off.empty() ? 0 : row_off[(size_t)segments()]; }
+  // of the queue subscriptions
+  int64_t queue_segments() const { return (int64_t)seg_start.size() - segments(); }
+  int64_t queue_members() const { return row_off.empty() ? 0 : row_off.back() - subscribers(); }
 };
 
-// The segments of a record's value; false when it is not a valid record.
+// The segments of a record's value and whether it is a queue subscription; false when it
+// is not a valid record.
+bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out, bool* queue);
+// (the segments alone: a queue record is a valid record)
 bool topic_parse_record(const std::string& json, std::vector<TopicSegment>* out);
 // "<topic>/<name>" (a key below the service's prefix); false when it names no topic of [0, max_topics).
 bool topic_parse_key(const std::string& rest, int64_t max_topics, int64_t* topic, std::string* name);

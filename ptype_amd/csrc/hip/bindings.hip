@@ -153,11 +153,11 @@ void launch_reply_gather(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int,
 int64_t scatter_question_tile();
 int64_t scatter_expand_tile();
 void launch_scatter_count(int, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t,
-                          uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, int64_t);
+                          uintptr_t, int64_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int64_t);
 void launch_scatter_expand(int, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int64_t, int64_t, bool,
                            int64_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t,
                            uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
-                           int64_t);
+                           int64_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, uint64_t, bool);
 }  // namespace ptype
 
 using namespace ptype;
@@ -513,13 +513,14 @@ PYBIND11_MODULE(_hip, m) {
     d["max_step"] = kScatterMaxStep;
     d["ctr_words"] = kScatterCtrWords;
     d["max_segments"] = kScatterMaxSegments;
+    d["max_queues"] = kScatterMaxQueues;
     d["rules"] = py::make_tuple("ranges", "members", "topics");
     return d;
   }, "the constants of scatter.hpp: the most rows and questions of one expansion, the largest step, the counter words");
   m.def("scatter_count", &launch_scatter_count, py::arg("rule"), py::arg("q_actor"), py::arg("q_a0"), py::arg("Q"),
         py::arg("step"), py::arg("offsets"), py::arg("G"), py::arg("n"), py::arg("first"), py::arg("tsum"),
         py::arg("toob"), py::arg("tile_cap"), py::arg("ctr"), py::arg("stream"), py::arg("row_off") = 0,
-        py::arg("n_segs") = 0,
+        py::arg("n_segs") = 0, py::arg("q_off") = 0, py::arg("n_queues") = 0,
         "the count, scan and first launches: n[q], first[q] (the exclusive prefix of n) and ctr = [total, saturating; "
         "oob]; the host reads ctr before scatter_expand");
   m.def("scatter_expand", &launch_scatter_expand, py::arg("rule"), py::arg("q_actor"), py::arg("q_a0"), py::arg("q_a1"),
@@ -528,7 +529,9 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("n_members"), py::arg("first"), py::arg("n"), py::arg("total"), py::arg("capacity"),
         py::arg("out_actor"), py::arg("out_a0"), py::arg("out_a1"), py::arg("out_a2"), py::arg("out_method"),
         py::arg("out_group"), py::arg("stream"), py::arg("row_off") = 0, py::arg("seg_start") = 0,
-        py::arg("seg_stride") = 0, py::arg("n_segs") = 0,
+        py::arg("seg_stride") = 0, py::arg("n_segs") = 0, py::arg("q_off") = 0, py::arg("q_seg") = 0,
+        py::arg("n_queues") = 0, py::arg("n_all") = 0, py::arg("key") = 0, py::arg("seq") = 0,
+        py::arg("by_index") = false,
         "the expand launch over what scatter_count left: the `total` rows of the batch columns and of group (the "
         "question index), 1 <= total <= capacity");
 

@@ -40,8 +40,20 @@
 // block, to the segments of its first and last row with the 64-way search of the owners:
 // a giant topic of a million segments costs a tile two ballot searches and its quads a
 // bisection over at most 2048 segments.
+//
+// Queue subscriptions (QUEUES, a compile-time variant of the topics rule: a table without one
+// launches the instantiations it always did).  After the rows of a topic's ordinary
+// subscriptions comes one row per queue subscription of the topic.  A row with k >= the
+// topic's ordinary rows is queue subscription j = q_off[g] + (k - ordinary rows); its members
+// are the segments q_seg[j] .. q_seg[j + 1] - 1 (at most 1024: ten bisection steps), c =
+// row_off[q_seg[j + 1]] - row_off[q_seg[j]] of them, and the row goes to member
+// m = ((mix64(key[q]) >> 32) * c) >> 32, or (seq + q) % c by index (scatter.hpp).  Ordinary
+// rows keep their path; a tile inside one question narrows over the ordinary segments only,
+// and only when it starts in them (the queue rows of a question follow its ordinary rows).
 #include "common.hpp"
 #include "scatter.hpp"
+
+#include <type_traits>
 
 namespace ptype {
 
@@ -68,8 +80,21 @@ struct ScatterRule {
   const int64_t* row_off;
   const int* seg_start;
   const int* seg_stride;
-  int64_t n_segs;
+  int64_t n_segs;  // (the ordinary segments: seg_off's bound)
 };
+
+// Topics with queue subscriptions (QUEUES): row_off / seg_start / seg_stride hold n_all >=
+// n_segs segments.  The rule of the QUEUES kernels alone: the others keep their argument.
+struct ScatterQueueRule : ScatterRule {
+  const int64_t* q_off;
+  const int64_t* q_seg;
+  const int64_t* key;
+  int64_t n_queues, n_all;
+  uint64_t seq;
+  int by_index;
+};
+template <bool QUEUES>
+using ScatterRuleOf = std::conditional_t<QUEUES, ScatterQueueRule, ScatterRule>;
 
 struct ScatterQuestions {
   const int* actor;
@@ -109,9 +134,9 @@ __device__ __forceinline__ int64_t scatter_seg_clamp(int64_t s, int64_t n_segs) 
   return s < 0 ? 0 : s > n_segs ? n_segs : s;
 }
 
-template <int RULE>
+template <int RULE, bool QUEUES = false>
 __global__ __launch_bounds__(kScatterThreads) void scatter_count_kernel(
-    ScatterRule r, const int* __restrict__ q_actor, const int64_t* __restrict__ q_a0, int64_t Q, int* __restrict__ n,
+    ScatterRuleOf<QUEUES> r, const int* __restrict__ q_actor, const int64_t* __restrict__ q_a0, int64_t Q, int* __restrict__ n,
     unsigned long long* __restrict__ first, unsigned long long* __restrict__ tsum, unsigned long long* __restrict__ toob) {
   __shared__ unsigned long long part[kScatterQPer * kScatterWaves];
   __shared__ unsigned oob_wave[kScatterWaves];
@@ -139,6 +164,10 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_count_kernel(
         if (g >= 0 && g < r.G) {
           const int64_t s0 = scatter_seg_clamp(r.offsets[g], r.n_segs), s1 = scatter_seg_clamp(r.offsets[g + 1], r.n_segs);
           if (s1 > s0) v[j] = (uint64_t)(r.row_off[s1] - r.row_off[s0]);
+          if constexpr (QUEUES) {  // one row per queue subscription of the topic
+            const int64_t j0 = scatter_seg_clamp(r.q_off[g], r.n_queues), j1 = scatter_seg_clamp(r.q_off[g + 1], r.n_queues);
+            if (j1 > j0) v[j] += (uint64_t)(j1 - j0);
+          }
         } else {
           ++n_oob;
         }
@@ -251,6 +280,14 @@ struct ScatterQ {
   int s0, s1;                 // topics: the topic's segments [s0, s1)
   int16_t method;
 };
+// Topics with queue subscriptions: also the topic's ordinary rows, its first queue
+// subscription, and what picks the member (mix64 of the key, or seq + q by index).
+struct ScatterQueueQ : ScatterQ {
+  int64_t nord, qj;
+  uint64_t pick;
+};
+template <bool QUEUES>
+using ScatterQOf = std::conditional_t<QUEUES, ScatterQueueQ, ScatterQ>;
 
 // The segment a topics quad stands in: its rows [lo, hi) of row_off's space and its actors.
 struct ScatterSeg {
@@ -277,10 +314,11 @@ __device__ __forceinline__ int scatter_seg_find(const ScatterRule& r, int lo, in
   return lo;
 }
 
-template <int RULE, bool MCOL>
-__device__ __forceinline__ ScatterQ scatter_question(const ScatterRule& r, const ScatterQuestions& qs,
-                                                     const int64_t* __restrict__ first, int q) {
-  ScatterQ d{};
+template <int RULE, bool MCOL, bool QUEUES>
+__device__ __forceinline__ ScatterQOf<QUEUES> scatter_question(const ScatterRuleOf<QUEUES>& r,
+                                                               const ScatterQuestions& qs,
+                                                               const int64_t* __restrict__ first, int q) {
+  ScatterQOf<QUEUES> d{};
   d.first = first[q];
   if constexpr (RULE == kScatterRanges) {
     d.a2 = qs.a0[q];
@@ -288,6 +326,16 @@ __device__ __forceinline__ ScatterQ scatter_question(const ScatterRule& r, const
     const int64_t g = qs.actor[q];
     if constexpr (RULE == kScatterMembers) {
       d.off = g >= 0 && g < r.G ? r.offsets[g] : 0;
+    } else if constexpr (QUEUES) {
+      // (row_off holds n_all + 1 >= n_segs + 1 entries; a topic may have no ordinary segment, s0 == s1)
+      const bool in = g >= 0 && g < r.G;
+      d.s0 = in ? (int)scatter_seg_clamp(r.offsets[g], r.n_segs) : 0;
+      d.s1 = in ? (int)scatter_seg_clamp(r.offsets[g + 1], r.n_segs) : 0;
+      if (d.s1 < d.s0) d.s1 = d.s0;
+      d.off = r.row_off[d.s0];
+      d.nord = r.row_off[d.s1] - d.off;
+      d.qj = in ? scatter_seg_clamp(r.q_off[g], r.n_queues) : 0;
+      d.pick = r.by_index ? r.seq + (uint64_t)q : mix64((uint64_t)r.key[q]);
     } else {
       const bool in = g >= 0 && g < r.G;
       d.s0 = in ? (int)scatter_seg_clamp(r.offsets[g], r.n_segs) : 0;
@@ -304,8 +352,23 @@ __device__ __forceinline__ ScatterQ scatter_question(const ScatterRule& r, const
   return d;
 }
 
-template <int RULE, bool MCOL>
-__global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(ScatterRule r, ScatterQuestions qs,
+// The actor a queue row goes to: queue subscription j of the table, picked by `pick`.
+__device__ __forceinline__ int scatter_queue_actor(const ScatterQueueRule& r, int64_t j, uint64_t pick) {
+  j = j < 0 ? 0 : j >= r.n_queues ? r.n_queues - 1 : j;  // (a row past the total only; n_queues >= 1)
+  int64_t a = scatter_seg_clamp(r.q_seg[j], r.n_all), b = scatter_seg_clamp(r.q_seg[j + 1], r.n_all);
+  a = a >= r.n_all ? r.n_all - 1 : a;  // (n_all >= 1)
+  b = b <= a ? a + 1 : b;
+  const int64_t lo = r.row_off[a];
+  uint64_t c = (uint64_t)(r.row_off[b] - lo);  // 1 <= c <= 2^31 - 1
+  c = c < 1 ? 1 : c > 0x7fffffffull ? 0x7fffffffull : c;  // (never taken: m stays inside the subscription's rows)
+  const uint64_t m = r.by_index ? pick % c : ((pick >> 32) * c) >> 32;
+  const int64_t at = lo + (int64_t)m;
+  const int s = scatter_seg_find(r, (int)a, (int)b, at);
+  return (int)((int64_t)r.seg_start[s] + (int64_t)r.seg_stride[s] * (at - r.row_off[s]));
+}
+
+template <int RULE, bool MCOL, bool QUEUES = false>
+__global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(ScatterRuleOf<QUEUES> r, ScatterQuestions qs,
                                                                           const int64_t* __restrict__ first,
                                                                           const int* __restrict__ n, int Q,
                                                                           int64_t total, ScatterOut out) {
@@ -327,13 +390,19 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
   int ts_lo = -1, ts_hi = -1;
   if constexpr (RULE == kScatterTopics) {
     if (q_lo == q_hi) {  // (block-uniform)
-      const ScatterQ d = scatter_question<RULE, false>(r, qs, first, q_lo);
+      const ScatterQOf<QUEUES> d = scatter_question<RULE, false, QUEUES>(r, qs, first, q_lo);
       int64_t at = d.off + (row0 - d.first);
       at = at < d.off ? d.off : at;
-      ts_lo = scatter_owner(r.row_off, d.s1, at, d.s0, lane);
-      ts_lo = ts_lo < d.s0 ? d.s0 : ts_lo;
-      ts_hi = scatter_owner(r.row_off, d.s1, at + rows - 1, ts_lo, lane);
-      ts_hi = (ts_hi < ts_lo ? ts_lo : ts_hi) + 1;
+      // (QUEUES: a tile that starts in the question's queue rows holds no ordinary row; one that ends
+      // in them finds the topic's last ordinary segment for its last row)
+      bool narrow = true;
+      if constexpr (QUEUES) narrow = at - d.off < d.nord;  // (block-uniform)
+      if (narrow) {
+        ts_lo = scatter_owner(r.row_off, d.s1, at, d.s0, lane);
+        ts_lo = ts_lo < d.s0 ? d.s0 : ts_lo;
+        ts_hi = scatter_owner(r.row_off, d.s1, at + rows - 1, ts_lo, lane);
+        ts_hi = (ts_hi < ts_lo ? ts_lo : ts_hi) + 1;
+      }
     }
   }
   __syncthreads();
@@ -380,7 +449,7 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
     int actor[4], group[4];
     int64_t a0[4], a1[4], a2[4];
     int16_t method[4];
-    ScatterQ d{};
+    ScatterQOf<QUEUES> d{};
     ScatterSeg sg{};
     int have = -1;
 #pragma unroll
@@ -388,7 +457,7 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
       int q = max(own[j][c], carry);
       q = q < 0 ? 0 : q >= Q ? Q - 1 : q;  // (never taken: position 0 holds q_lo <= every owner < Q)
       const bool fresh = q != have;
-      if (fresh) d = scatter_question<RULE, MCOL>(r, qs, first, q), have = q;
+      if (fresh) d = scatter_question<RULE, MCOL, QUEUES>(r, qs, first, q), have = q;
       const int64_t row = row0 + p + c;
       const int64_t k = row - d.first;
       group[c] = q;
@@ -404,6 +473,13 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_expand_kernel(Scatter
         actor[c] = r.members[at];
         a0[c] = d.a0, a1[c] = d.a1, a2[c] = d.a2;
       } else {
+        if constexpr (QUEUES) {
+          if (k >= d.nord) {  // a queue row: they follow the question's ordinary rows
+            actor[c] = scatter_queue_actor(r, d.qj + (k - d.nord), d.pick);
+            a0[c] = d.a0, a1[c] = d.a1, a2[c] = d.a2;
+            continue;
+          }
+        }
         const int64_t at = d.off + k;
         if (fresh) {  // one search per question of the quad ...
           const int lo = ts_lo >= 0 ? ts_lo : d.s0, hi = ts_lo >= 0 ? ts_hi : d.s1;
@@ -450,7 +526,7 @@ int64_t scatter_question_tile() { return kScatterQTile; }
 int64_t scatter_expand_tile() { return kScatterTile; }
 
 static void scatter_check_rule(int rule, int64_t Q, uintptr_t q_actor, uintptr_t q_a0, int64_t step, uintptr_t offsets,
-                               int64_t G, uintptr_t row_off, int64_t n_segs) {
+                               int64_t G, uintptr_t row_off, int64_t n_segs, uintptr_t q_off, int64_t n_queues) {
   if (rule < 0 || rule >= kScatterRules) throw std::invalid_argument("scatter: unknown rule");
   if (Q < 1 || Q > kScatterMaxQuestions) throw std::invalid_argument("scatter: Q must be in [1, 2^26]");
   if ((q_a0 & 7u) || (q_actor & 3u) || (offsets & 7u)) throw std::invalid_argument("scatter: misaligned column");
@@ -463,17 +539,23 @@ static void scatter_check_rule(int rule, int64_t Q, uintptr_t q_actor, uintptr_t
     if (rule == kScatterTopics) {
       if (!row_off || (row_off & 7u)) throw std::invalid_argument("scatter: topics needs an aligned row_off");
       if (n_segs < 0 || n_segs > kScatterMaxSegments) throw std::invalid_argument("scatter: n_segs must be in [0, 2^24]");
+      if (n_queues < 0 || n_queues > kScatterMaxQueues) throw std::invalid_argument("scatter: n_queues must be in [0, 2^24]");
+      if (n_queues && (!q_off || (q_off & 7u))) throw std::invalid_argument("scatter: queue subscriptions need an aligned q_off");
+    } else if (n_queues) {
+      throw std::invalid_argument("scatter: queue subscriptions belong to the topics rule");
     }
   }
 }
 
 // Count, scan, first: n int32[Q], first int64[Q], the counters (scatter.hpp).  `tsum` and
 // `toob`: `tile_cap` u64 each of scratch, tile_cap >= ceil(Q / scatter_question_tile()).
-// The question columns: Q elements, any natural alignment.
+// The question columns: Q elements, any natural alignment.  Topics with n_queues >= 1 queue
+// subscriptions: q_off int64[G + 1], and the count kernel's QUEUES variant runs.
 void launch_scatter_count(int rule, uintptr_t q_actor, uintptr_t q_a0, int64_t Q, int64_t step, uintptr_t offsets,
                           int64_t G, uintptr_t n, uintptr_t first, uintptr_t tsum, uintptr_t toob, int64_t tile_cap,
-                          uintptr_t ctr, uintptr_t stream, uintptr_t row_off, int64_t n_segs) {
-  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs);
+                          uintptr_t ctr, uintptr_t stream, uintptr_t row_off, int64_t n_segs, uintptr_t q_off,
+                          int64_t n_queues) {
+  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs, q_off, n_queues);
   const int64_t tiles = (Q + kScatterQTile - 1) / kScatterQTile;
   if (tiles > tile_cap) throw std::invalid_argument("scatter: the tile scratch is too small for Q");
   if (!n || !first || !tsum || !toob || !ctr) throw std::invalid_argument("scatter: null output or scratch");
@@ -483,12 +565,21 @@ void launch_scatter_count(int rule, uintptr_t q_actor, uintptr_t q_a0, int64_t Q
   r.offsets = (const int64_t*)offsets;
   r.G = G;
   r.row_off = (const int64_t*)row_off, r.n_segs = n_segs;
-  auto kernel = rule == kScatterRanges    ? scatter_count_kernel<kScatterRanges>
-                : rule == kScatterMembers ? scatter_count_kernel<kScatterMembers>
-                                          : scatter_count_kernel<kScatterTopics>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kScatterThreads), 0, as_stream(stream), r,
-                     (const int*)q_actor, (const int64_t*)q_a0, Q, (int*)n, (unsigned long long*)first,
-                     (unsigned long long*)tsum, (unsigned long long*)toob);
+  if (rule == kScatterTopics && n_queues) {  // the table has a queue subscription
+    ScatterQueueRule qr{};
+    static_cast<ScatterRule&>(qr) = r;
+    qr.q_off = (const int64_t*)q_off, qr.n_queues = n_queues;
+    hipLaunchKernelGGL((scatter_count_kernel<kScatterTopics, true>), dim3((unsigned)tiles), dim3(kScatterThreads), 0,
+                       as_stream(stream), qr, (const int*)q_actor, (const int64_t*)q_a0, Q, (int*)n, (unsigned long long*)first,
+                       (unsigned long long*)tsum, (unsigned long long*)toob);
+  } else {
+    auto kernel = rule == kScatterRanges    ? scatter_count_kernel<kScatterRanges>
+                  : rule == kScatterMembers ? scatter_count_kernel<kScatterMembers>
+                                            : scatter_count_kernel<kScatterTopics>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kScatterThreads), 0, as_stream(stream), r,
+                       (const int*)q_actor, (const int64_t*)q_a0, Q, (int*)n, (unsigned long long*)first,
+                       (unsigned long long*)tsum, (unsigned long long*)toob);
+  }
   PT_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(scatter_scan_kernel, dim3(1), dim3(kScatterThreads), 0, as_stream(stream),
                      (unsigned long long*)tsum, (const unsigned long long*)toob, tiles, (unsigned long long*)ctr);
@@ -506,15 +597,19 @@ using ScatterExpandKernel = void (*)(ScatterRule, ScatterQuestions, const int64_
 // actor / group int32, a0 (a1, a2: ranges always, members and topics when the question has them)
 // int64, method int16 when the questions carry a method column; all 16-byte aligned (method 8).
 // Topics: offsets = seg_off int64[G + 1], row_off int64[n_segs + 1], seg_start / seg_stride
-// int32[n_segs], 1 <= n_segs <= 2^24.
+// int32[n_segs], 1 <= n_segs <= 2^24.  Topics with n_queues >= 1 queue subscriptions run the QUEUES
+// variant: row_off int64[n_all + 1], seg_start / seg_stride int32[n_all] with the queue segments
+// after the n_segs ordinary ones (1 <= n_all <= 2^24, n_segs >= 0), q_off int64[G + 1], q_seg
+// int64[n_queues + 1], `key` int64[Q] (by key) or `seq` (by index); without one, today's kernels.
 void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_t q_a1, uintptr_t q_a2, uintptr_t q_method,
                            int64_t Q, int64_t step, int64_t n_actors, int64_t actor_base, bool has_lo, int64_t first_lo,
                            uintptr_t offsets, uintptr_t members, int64_t G, int64_t n_members, uintptr_t first,
                            uintptr_t n, int64_t total, int64_t capacity, uintptr_t out_actor, uintptr_t out_a0,
                            uintptr_t out_a1, uintptr_t out_a2, uintptr_t out_method, uintptr_t out_group,
                            uintptr_t stream, uintptr_t row_off, uintptr_t seg_start, uintptr_t seg_stride,
-                           int64_t n_segs) {
-  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs);
+                           int64_t n_segs, uintptr_t q_off, uintptr_t q_seg, int64_t n_queues, int64_t n_all,
+                           uintptr_t key, uint64_t seq, bool by_index) {
+  scatter_check_rule(rule, Q, q_actor, q_a0, step, offsets, G, row_off, n_segs, q_off, n_queues);
   if (capacity < 1 || capacity > kScatterMaxRows) throw std::invalid_argument("scatter: capacity must be in [1, 2^31 - 2]");
   if (total < 1 || total > capacity) throw std::invalid_argument("scatter: total must be in [1, capacity]");
   if (!first || !n || !out_actor || !out_a0 || !out_group) throw std::invalid_argument("scatter: null output");
@@ -524,6 +619,7 @@ void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_
   if (!q_a0) throw std::invalid_argument("scatter: the questions need an a0 column");
   if ((q_method != 0) != (out_method != 0)) throw std::invalid_argument("scatter: a method column in, a method column out");
   ScatterRule r{};
+  ScatterQueueRule qa{};
   r.step = (uint64_t)(rule == kScatterRanges ? step : 1);
   if (rule == kScatterRanges) {
     if (n_actors < 1 || n_actors > 0x7fffffffll) throw std::invalid_argument("scatter: n_actors must be in [1, 2^31 - 1]");
@@ -540,16 +636,34 @@ void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_
         throw std::invalid_argument("scatter: members needs a non-empty member list");
       r.members = (const int*)members, r.n_members = n_members;
     } else {
-      if (!seg_start || !seg_stride || n_segs < 1) throw std::invalid_argument("scatter: topics needs a non-empty segment table");
+      if (!seg_start || !seg_stride || (n_queues ? n_all : n_segs) < 1)
+        throw std::invalid_argument("scatter: topics needs a non-empty segment table");
       if ((seg_start | seg_stride) & 3u) throw std::invalid_argument("scatter: misaligned segment table");
       r.row_off = (const int64_t*)row_off, r.seg_start = (const int*)seg_start, r.seg_stride = (const int*)seg_stride;
       r.n_segs = n_segs;
+      if (n_queues) {
+        if (!q_seg || (q_seg & 7u)) throw std::invalid_argument("scatter: queue subscriptions need an aligned q_seg");
+        if (n_all < n_segs || n_all > kScatterMaxSegments)
+          throw std::invalid_argument("scatter: n_all must be in [n_segs, 2^24]");
+        if (!by_index && (!key || (key & 7u))) throw std::invalid_argument("scatter: by key needs an aligned key column");
+        qa.q_off = (const int64_t*)q_off, qa.q_seg = (const int64_t*)q_seg, qa.key = (const int64_t*)key;
+        qa.n_queues = n_queues, qa.n_all = n_all, qa.seq = seq, qa.by_index = by_index ? 1 : 0;
+      }
     }
   }
   const ScatterQuestions qs{(const int*)q_actor, (const int64_t*)q_a0, (const int64_t*)q_a1, (const int64_t*)q_a2,
                             (const int16_t*)q_method};
   const ScatterOut out{(int*)out_actor,  (int64_t*)out_a0,     (int64_t*)out_a1,
                        (int64_t*)out_a2, (int16_t*)out_method, (int*)out_group};
+  const dim3 grid((unsigned)((total + kScatterTile - 1) / kScatterTile));
+  if (rule == kScatterTopics && n_queues) {  // the table has a queue subscription
+    static_cast<ScatterRule&>(qa) = r;
+    auto kernel = q_method ? scatter_expand_kernel<kScatterTopics, true, true> : scatter_expand_kernel<kScatterTopics, false, true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kScatterThreads), 0, as_stream(stream), qa, qs, (const int64_t*)first,
+                       (const int*)n, (int)Q, total, out);
+    PT_HIP_CHECK(hipGetLastError());
+    return;
+  }
   ScatterExpandKernel kernel;
   if (rule == kScatterRanges)
     kernel = q_method ? scatter_expand_kernel<kScatterRanges, true> : scatter_expand_kernel<kScatterRanges, false>;
@@ -557,8 +671,8 @@ void launch_scatter_expand(int rule, uintptr_t q_actor, uintptr_t q_a0, uintptr_
     kernel = q_method ? scatter_expand_kernel<kScatterMembers, true> : scatter_expand_kernel<kScatterMembers, false>;
   else
     kernel = q_method ? scatter_expand_kernel<kScatterTopics, true> : scatter_expand_kernel<kScatterTopics, false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + kScatterTile - 1) / kScatterTile)), dim3(kScatterThreads), 0,
-                     as_stream(stream), r, qs, (const int64_t*)first, (const int*)n, (int)Q, total, out);
+  hipLaunchKernelGGL(kernel, grid, dim3(kScatterThreads), 0, as_stream(stream), r, qs, (const int64_t*)first,
+                     (const int*)n, (int)Q, total, out);
   PT_HIP_CHECK(hipGetLastError());
 }
 

@@ -18,6 +18,19 @@
 //            row_off[seg_off[g]], 0 for g outside [0, G) (counted in `oob`); row k belongs to
 //            the segment s of g with row_off[s] <= row_off[seg_off[g]] + k < row_off[s + 1];
 //            a0 / a1 / a2 the question's.  No per-subscriber table exists.
+//            Queue subscriptions (competing consumers): the table may also hold NQ of them, their
+//            segments after the S ordinary ones in row_off / seg_start / seg_stride (seg_off[G]
+//            = S keeps bounding the ordinary ones).  Topic g owns the queue subscriptions
+//            q_off[g] .. q_off[g + 1] - 1 (q_off int64[G + 1]), queue subscription j the segments
+//            q_seg[j] .. q_seg[j + 1] - 1 (q_seg int64[NQ + 1], 1 to 1024 each) and their
+//            c = row_off[q_seg[j + 1]] - row_off[q_seg[j]] members, 1 <= c <= 2^31 - 1.  After
+//            its ordinary rows a question has ONE row per queue subscription of its topic, in
+//            q_off's order: n grows by q_off[g + 1] - q_off[g].  That row goes to member
+//              by key    m = ((mix64(key[q]) >> 32) * c) >> 32   (u64; key int64[Q]; mix64 of common.hpp)
+//              by index  m = ((seq + q) mod 2^64) mod c           (seq: a u64 of the caller's)
+//            of the subscription: the segment s with row_off[s] <= row_off[q_seg[j]] + m <
+//            row_off[s + 1].  A compile-time variant of this rule, launched only for a table
+//            with NQ >= 1; a table without one runs the kernels it always ran.
 // The method is the question's (one id, or an int16 column copied per row); `group`
 // holds the question index of every row.
 //
@@ -40,5 +53,7 @@ constexpr int64_t kScatterMaxQuestions = 1ll << 26;
 constexpr int64_t kScatterMaxStep = 0x7fffffffll;
 // segments of one topic table: a segment index fits the int of the owner search
 constexpr int64_t kScatterMaxSegments = 1ll << 24;
+// queue subscriptions of one topic table
+constexpr int64_t kScatterMaxQueues = 1ll << 24;
 
 }  // namespace ptype

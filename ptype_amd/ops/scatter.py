@@ -34,6 +34,27 @@ the segment ``s`` of ``g`` with ``row_off[s] <= row_off[seg_off[g]] + k < row_of
 gets ``actor = seg_start[s] + seg_stride[s] * (row_off[seg_off[g]] + k - row_off[s])`` and
 the question's own ``a0``, ``a1``, ``a2``.  Every expand reads the table as it then stands.
 
+Queue subscriptions (``Scatter.topics(table, by="key")``, ``expand(questions, key=None)``).  The
+table may also hold queue subscriptions (competing consumers; ``ops/topics.py``): ``q_off``
+int64[G + 1] (topic ``g`` owns the queue subscriptions ``q_off[g] .. q_off[g + 1] - 1``) and
+``q_seg`` int64[NQ + 1] (queue subscription ``j`` owns the segments ``q_seg[j] .. q_seg[j + 1] -
+1``, which follow the ordinary ones in the segment arrays, and their ``c = row_off[q_seg[j + 1]]
+- row_off[q_seg[j]]`` members).  After the rows of its topic's ordinary subscriptions a question
+gets ONE row per queue subscription of the topic, in ``q_off``'s order, so ``n[q]`` grows by
+``q_off[g + 1] - q_off[g]``.  That row goes to member ``m`` of the subscription -- the segment
+``s`` with ``row_off[s] <= row_off[q_seg[j]] + m < row_off[s + 1]`` -- where
+
+* ``by="key"`` (default): ``m = ((mix64(uint64(key[q])) >> 32) * c) >> 32`` in unsigned 64-bit
+  arithmetic (``ops.table.mix64``; multiply-shift, not ``%``: a 64-bit remainder is a long
+  emulated sequence on the device).  ``key`` is an int64[Q] column given to ``expand``, by
+  default the questions' ``a0``.  The same key and the same membership always give the same
+  member: per-key ordering.
+* ``by="index"``: ``m = ((seq + q) mod 2**64) mod c``; ``seq`` is a u64 counter of the Scatter
+  that starts at 0 and advances by Q after every expansion that used it (one over a table
+  with a queue subscription): the replica router's round robin applied to publications.
+
+A table without a queue subscription launches exactly the kernels it always did.
+
 Either way the method is the question's: one id, or an int16 column copied per row.
 
 ``expand(questions)`` returns an ``Expansion`` whose tensors are views, of length T and
@@ -66,6 +87,7 @@ MAX_ROWS = (1 << 31) - 2        # scatter.hpp kScatterMaxRows
 MAX_QUESTIONS = 1 << 26         # scatter.hpp kScatterMaxQuestions
 MAX_STEP = (1 << 31) - 1        # scatter.hpp kScatterMaxStep
 MAX_SEGMENTS = 1 << 24          # scatter.hpp kScatterMaxSegments
+MAX_QUEUES = 1 << 24            # scatter.hpp kScatterMaxQueues
 U64_MAX = (1 << 64) - 1
 I32_MAX = (1 << 31) - 1
 
@@ -89,6 +111,8 @@ def scatter_counts(rule: "Scatter", questions: MsgBatch):
         inside = (g >= 0) & (g < t["seg_off"].size - 1)
         gi = np.where(inside, g, 0)
         rows = t["row_off"][t["seg_off"][gi + 1]] - t["row_off"][t["seg_off"][gi]]
+        if "q_off" in t:  # one row per queue subscription of the topic
+            rows = rows + (t["q_off"][gi + 1] - t["q_off"][gi])
         n = np.where(inside, rows, 0).astype(np.uint64)
         oob = int((~inside).sum())
     else:
@@ -102,10 +126,28 @@ def scatter_counts(rule: "Scatter", questions: MsgBatch):
     return n, total, oob
 
 
-def scatter_ref(rule: "Scatter", questions: MsgBatch) -> dict:
+def queue_pick(c, key=None, index=None) -> np.ndarray:
+    """The member (uint64, in ``[0, c)``) of a queue subscription of ``c`` members (``1 <= c <=
+    2**31 - 1``; a scalar or an array) that a publication reaches: by ``key`` (int64),
+    ``((mix64(uint64(key)) >> 32) * c) >> 32``, or by ``index`` (``(seq + q) mod 2**64`` as
+    uint64), ``index mod c``."""
+    from .table import mix64
+
+    c = np.asarray(c).astype(np.uint64)
+    if (key is None) == (index is None):
+        raise ValueError("queue_pick: exactly one of key= and index=")
+    if index is not None:
+        return np.asarray(index).astype(np.uint64) % c
+    h = mix64(np.asarray(key).astype(np.int64).astype(np.uint64))
+    return ((h >> np.uint64(32)) * c) >> np.uint64(32)  # ((< 2**32) * (< 2**31): no overflow)
+
+
+def scatter_ref(rule: "Scatter", questions: MsgBatch, key=None) -> dict:
     """The spec in numpy: ``{"actor" int32[T], "a0" / "a1" / "a2" int64[T] (members, topics: None
     where the questions have none), "method" (the id, or int16[T]), "group" int32[T],
-    "first" int64[Q], "n" int32[Q], "total", "oob"}`` as CPU tensors and Python ints."""
+    "first" int64[Q], "n" int32[Q], "total", "oob"}`` as CPU tensors and Python ints.  Topics
+    with queue subscriptions: ``key`` is the int64[Q] key column (default: ``a0``) of
+    ``by="key"``; ``by="index"`` reads ``rule.seq`` and leaves it as it is."""
     n64, total, oob = scatter_counts(rule, questions)
     if total > MAX_ROWS:
         raise ValueError(f"scatter: {total} rows exceed the most one expansion holds ({MAX_ROWS})")
@@ -131,6 +173,20 @@ def scatter_ref(rule: "Scatter", questions: MsgBatch) -> dict:
         else:
             t = rule.table.host
             at = t["row_off"][t["seg_off"][g]] + k
+            if "q_off" in t and t["q_seg"].size > 1:
+                ordinary = t["row_off"][t["seg_off"][g + 1]] - t["row_off"][t["seg_off"][g]]
+                isq = k >= ordinary  # the queue rows follow the topic's ordinary rows
+                j = (t["q_off"][g] + (k - ordinary))[isq]
+                lo = t["row_off"][t["q_seg"][j]]
+                c = t["row_off"][t["q_seg"][j + 1]] - lo
+                gq = group[isq]
+                if rule.by == "index":
+                    with np.errstate(over="ignore"):
+                        m = queue_pick(c, index=np.uint64(rule.seq) + gq.astype(np.uint64))
+                else:
+                    kcol = _np(questions.a0 if key is None else key, np.int64)
+                    m = queue_pick(c, key=kcol[gq])
+                at[isq] = lo + m.astype(np.int64)
             seg = np.searchsorted(t["row_off"], at, side="right") - 1  # (row_off is strictly increasing)
             actor = t["seg_start"][seg].astype(np.int64) + t["seg_stride"][seg].astype(np.int64) * (at - t["row_off"][seg])
         a0 = _np(questions.a0, np.int64)[group]
@@ -211,8 +267,9 @@ class Scatter:
         self.step, self.n_actors, self.first_lo, self.actor_base = 1, 1, None, 0
         # members
         self.G, self.offsets, self.members_, self.offsets_host, self.members_host = 0, None, None, None, None
-        # topics
+        # topics; queue subscriptions: the member by the key's hash or by index, the index counter (u64)
         self.table = None
+        self.by, self.seq = "key", 0
 
     # ------------------------------------------------------------------ the three rules
     @classmethod
@@ -239,10 +296,14 @@ class Scatter:
         return s
 
     @classmethod
-    def topics(cls, table, capacity: int = 1 << 20, q_capacity: int | None = None) -> "Scatter":
+    def topics(cls, table, capacity: int = 1 << 20, q_capacity: int | None = None, by: str = "key") -> "Scatter":
         """``table``: an ``ops.topics.TopicTable`` (or anything with its ``host`` dict of numpy
-        arrays, ``device_arrays(device)`` and ``max_topics``); ``set_table`` replaces it."""
+        arrays, ``device_arrays(device)`` and ``max_topics``); ``set_table`` replaces it.  ``by``:
+        how a queue subscription's member is picked, ``"key"`` or ``"index"`` (module docstring)."""
+        if by not in ("key", "index"):
+            raise ValueError('Scatter.topics: by must be "key" or "index"')
         s = cls("topics", capacity, q_capacity)
+        s.by = by
         s.set_table(table)
         return s
 
@@ -314,11 +375,22 @@ class Scatter:
             raise ValueError(f"Scatter.expand: {Q} questions exceed q_capacity {self.q_capacity}")
         return Q
 
-    def expand(self, questions: MsgBatch) -> Expansion:
+    def _queues(self) -> bool:
+        """Whether the rule reads a table that holds a queue subscription."""
+        return self.rule == "topics" and int(self.table.host.get("q_seg", np.zeros(1)).size) > 1
+
+    def expand(self, questions: MsgBatch, key: torch.Tensor | None = None) -> Expansion:
         """Expand ``questions`` into the buffers (module docstring).  On a GPU: four
-        launches on the current stream and one 16-byte host read."""
+        launches on the current stream and one 16-byte host read.  ``key``: the int64[Q] key
+        column of a topics rule's queue subscriptions (default: the questions' ``a0``)."""
         Q = self._check(questions)
         dev = questions.actor.device
+        if key is not None:
+            if self.rule != "topics":
+                raise ValueError("Scatter.expand: key= belongs to the topics rule")
+            if not isinstance(key, torch.Tensor) or key.dtype != torch.int64 or key.dim() != 1 or key.numel() != Q or \
+                    key.device != dev:
+                raise ValueError("Scatter.expand: key must be an int64[Q] tensor on the questions' device")
         if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise ValueError("Scatter.expand inside a captured Send: the total of the expansion is read on the host "
                              "(expand first, capture the Send of the prepared Expansion)")
@@ -333,7 +405,7 @@ class Scatter:
         if dev.type != "cuda":
             _, total, oob = scatter_counts(self, questions)
             self._refuse(total)
-            ref = scatter_ref(self, questions)
+            ref = scatter_ref(self, questions, key=key)
             if mcol and self.method is None:
                 self.method = torch.empty(self.capacity, dtype=torch.int16)
             for name in ("actor", "a0", "a1", "a2", "group"):
@@ -349,6 +421,8 @@ class Scatter:
             c = (lambda t: None if t is None else t.contiguous())
             cols = (c(questions.actor), c(questions.a0), c(questions.a1) if members else None,
                     c(questions.a2) if members else None, c(questions.method) if mcol else None)
+            if self._queues() and self.by == "key":
+                cols += (cols[1] if key is None else key.contiguous(),)
             self._count(cols, Q)
             ctr = self.ctr.cpu()  # the host read of an expansion: 16 bytes
             total, oob = int(ctr[0]) & U64_MAX, int(ctr[1])
@@ -357,6 +431,8 @@ class Scatter:
                 self.method = torch.empty(self.capacity, dtype=torch.int16, device=dev)
             if total:
                 self._fill(cols, Q, total)
+        if Q and self.by == "index" and self._queues():
+            self.seq = (self.seq + Q) & U64_MAX  # (after every expansion that used it, refused ones apart)
         batch = MsgBatch(self.actor[:total], self.a0[:total], self.a1[:total] if has1 else None,
                          self.a2[:total] if has2 else None, self.method[:total] if mcol else int(questions.method))
         return Expansion(self, batch, self.group[:total], self.first[:Q], self.n[:Q], total, oob)
@@ -365,10 +441,10 @@ class Scatter:
         """The count, scan and first launches over the question columns ``cols`` (actor, a0,
         a1, a2, method; contiguous or None): ``n``, ``first`` and ``ctr`` on the device."""
         if self.rule == "topics":
-            seg_off, G, row_off, n_segs, _, _ = self.table.launch_args(self.device)
+            seg_off, G, row_off, n_segs, _, _, q_off, _, n_queues, _ = self._table_args()
             hip().scatter_count(2, _ptr(cols[0]), _ptr(cols[1]), Q, 1, seg_off, G, _ptr(self.n), _ptr(self.first),
                                 _ptr(self.tsum), _ptr(self.toob), self.tile_cap, _ptr(self.ctr), raw_stream(self.device),
-                                row_off, n_segs)
+                                row_off, n_segs, q_off if n_queues else 0, n_queues)
             return
         hip().scatter_count(RULES.index(self.rule), _ptr(cols[0]), _ptr(cols[1]), Q, self.step, _ptr(self.offsets),
                             self.G, _ptr(self.n), _ptr(self.first), _ptr(self.tsum), _ptr(self.toob), self.tile_cap,
@@ -380,12 +456,14 @@ class Scatter:
         members = self.rule != "ranges"
         out = (lambda buf, col: _ptr(buf) if not members or col is not None else 0)
         if self.rule == "topics":
-            seg_off, G, row_off, n_segs, seg_start, seg_stride = self.table.launch_args(self.device)
+            seg_off, G, row_off, n_segs, seg_start, seg_stride, q_off, q_seg, n_queues, n_all = self._table_args()
+            queue = () if not n_queues else (q_off, q_seg, n_queues, n_all, 0 if self.by == "index" else _ptr(cols[5]),
+                                             self.seq if self.by == "index" else 0, self.by == "index")
             hip().scatter_expand(2, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), Q, 1, 1, 0,
                                  False, 0, seg_off, 0, G, 0, _ptr(self.first), _ptr(self.n), total, self.capacity,
                                  _ptr(self.actor), _ptr(self.a0), out(self.a1, cols[2]), out(self.a2, cols[3]),
                                  0 if cols[4] is None else _ptr(self.method), _ptr(self.group), raw_stream(self.device),
-                                 row_off, seg_start, seg_stride, n_segs)
+                                 row_off, seg_start, seg_stride, n_segs, *queue)
             return
         hip().scatter_expand(RULES.index(self.rule), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]),
                              _ptr(cols[4]), Q, self.step, self.n_actors, self.actor_base, self.first_lo is not None,
@@ -394,6 +472,11 @@ class Scatter:
                              total, self.capacity, _ptr(self.actor), _ptr(self.a0), out(self.a1, cols[2]),
                              out(self.a2, cols[3]), 0 if cols[4] is None else _ptr(self.method), _ptr(self.group),
                              raw_stream(self.device))
+
+    def _table_args(self):
+        """``TopicTable.launch_args`` (a table of four arrays has no queue subscription)."""
+        a = tuple(self.table.launch_args(self.device))
+        return a if len(a) >= 10 else a[:6] + (0, 0, 0, a[3])
 
     def _refuse(self, total: int) -> None:
         if total > self.capacity:

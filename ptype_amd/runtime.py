@@ -197,6 +197,7 @@ class DeviceRuntime:
             raise ValueError("max_topics must be in [1, 2**20]")
         self._topics: dict = {}
         self._topic_counters = {"publishes": 0, "publications": 0, "rows": 0, "oob": 0}
+        self._queue_rows = 0  # the queue-subscription rows published (Stats()["runtime"]["queues"])
         self.shards: dict[str, list[dict]] = {}
         self.mirror = None  # RegistryMirror (watch-driven) once attached to a control plane
         self.shard_lease = None
@@ -714,7 +715,8 @@ class DeviceRuntime:
                    torch.empty(0, dtype=torch.int32, device=self.device))
         return Redrive(letters, out[0], out[1])
 
-    def ask(self, service: str | None, questions: B.MsgBatch, scatter, op: str = "sum", sentinel=None, **send_kw):
+    def ask(self, service: str | None, questions: B.MsgBatch, scatter, op: str = "sum", sentinel=None, key=None,
+            **send_kw):
         """Scatter-gather in one call (the optimus coordinator's ``splitWork`` ..
         ``watchReplies``, coordinator.go:67-98): ``scatter`` (an ``ops.scatter.Scatter``)
         expands the Q ``questions`` into T calls on the device, the calls go through
@@ -726,14 +728,15 @@ class DeviceRuntime:
         an Ask is refused under graph capture; more calls than a Send takes raise the
         Send's error before anything travels.  Each rank expands its own questions, there
         is no new collective: a rank whose expansion is empty joins the Send with an
-        empty batch, and at world 1 an empty expansion skips the Send."""
+        empty batch, and at world 1 an empty expansion skips the Send.  ``key``: the key column
+        of a topics rule's queue subscriptions (``publish``); any other rule refuses one."""
         from .ops.scatter import Answer
 
         if "gather" in send_kw:
             raise ValueError("ask: the gather is the expansion's own (op=, sentinel=)")
         if self._exchange is not None and self._exchange._capturing:
             raise ValueError("ask inside a captured Send: the total of the expansion is read on the host")
-        exp = scatter.expand(questions)
+        exp = scatter.expand(questions) if key is None else scatter.expand(questions, key=key)
         c = self._scatter_counters
         c["asks"] += 1
         c["questions"] += exp.Q
@@ -779,7 +782,8 @@ class DeviceRuntime:
             self._topics[service] = t
         return t
 
-    def publish(self, service: str | None, publications: B.MsgBatch, op: str = "sum", sentinel=None, **send_kw):
+    def publish(self, service: str | None, publications: B.MsgBatch, op: str = "sum", sentinel=None, key=None,
+                by: str | None = None, **send_kw):
         """Publish/subscribe in one call (Akka's ``DistributedPubSub`` ``Publish``): publication
         q -- its ``actor`` column names a topic -- becomes one call to every subscriber of the
         topic, expanded on the device from the store's subscriptions (``ops/topics.py``), sent,
@@ -787,14 +791,34 @@ class DeviceRuntime:
         table's scatter: everything ``ask`` documents holds unchanged (the Send keywords, the
         refusal under capture, each rank expanding its own publications, no new collective).
         A subscription is visible to a Publish once ``TopicTable.wait`` of its revision returned
-        (``Client.Subscribe`` waits for its own)."""
+        (``Client.Subscribe`` waits for its own).
+
+        Queue subscriptions (``Client.Subscribe(queue=True)``): after the calls to its topic's
+        ordinary subscribers a publication makes ONE call per queue subscription of the topic,
+        to the member picked ``by="key"`` (default: the hash of ``key[q]``, an int64[Q] column
+        that defaults to the publication's ``a0`` -- one key always reaches one member while the
+        membership stands) or ``by="index"`` (round robin over the table scatter's ``seq``
+        counter); ``ops/scatter.py`` has the arithmetic.  Over a table without a queue
+        subscription ``key`` and ``by`` change nothing."""
+        if by not in (None, "key", "index"):
+            raise ValueError('publish: by must be "key" or "index"')
         t = self._topics.get(self.service if service is None else service) or self.topics(service)
         if self._exchange is not None and self._exchange._capturing:
             raise ValueError("publish inside a captured Send: the total of the expansion is read on the host")
         t.apply()
+        t.scatter.by = by or "key"
+        if t.n_queues and publications.actor.numel():
+            # the queue rows of these publications, from the host's table: 4 bytes per publication read
+            g = publications.actor.detach().cpu().numpy().astype("int64")
+            q_off = t.host["q_off"]
+            g = g[(g >= 0) & (g < q_off.size - 1)]
+            queue_rows = int((q_off[g + 1] - q_off[g]).sum())
+        else:
+            queue_rows = 0
         a = self._scatter_counters
         questions, rows, oob = a["questions"], a["rows"], a["oob"]
-        out = self.ask(service, publications, t.scatter, op=op, sentinel=sentinel, **send_kw)
+        out = self.ask(service, publications, t.scatter, op=op, sentinel=sentinel, key=key, **send_kw)
+        self._queue_rows += queue_rows
         c = self._topic_counters
         c["publishes"] += 1
         c["publications"] += a["questions"] - questions
@@ -1282,6 +1306,8 @@ class DeviceRuntime:
         out["topics"] = dict(t.stats() if t is not None else {"topics": 0, "segments": 0, "subscribers": 0, "records": 0,
                                                               "bad_records": 0, "applied_rev": 0},
                              **self._topic_counters)
+        out["queues"] = dict(t.queue_stats() if t is not None else {"queues": 0, "members": 0, "segments": 0},
+                             rows=self._queue_rows)
         out["dead_letters"] = (self._dlq.read() if self._dlq is not None  # (one host read of the control line)
                                else {"entries": 0, "appended": 0, "unread": 0, "dropped": 0, "sends": 0, "torn": 0,
                                      "redrives": 0, "redriven": 0})
