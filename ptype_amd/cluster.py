@@ -377,6 +377,47 @@ class Client:
         kw.setdefault("dead_letter_tag", self._dead_letter_tag())
         return self._rt.redrive(self.service, max_letters, router=self._replica_router(), **kw)
 
+    def Schedule(self, batch, delay, tag: int | None = None):
+        """Delayed messages, the ``scheduleOnce`` / ``SendOnce`` / ``DelaySeconds`` of the batched
+        path: row ``i`` of ``batch`` is kept, with its whole call, in the runtime's timer queue
+        in HBM (ops/timers.py) and sent by the ``Tick()`` ``delay[i]`` ticks from now.  ``delay``
+        is an int or an int32 column; a row whose delay is outside ``[1, gpu.timer_horizon]`` is
+        not filed and counted in ``refused``.  ``tag`` defaults to this client's (FNV-1a64 of its
+        service, as for dead letters).  Returns an ``ops.timers.Scheduled``: ``n``, ``refused``,
+        ``first_ticket``, ``now``; raises ``ops.timers.TimerQueueFull``, with nothing filed, when the
+        ring (``gpu.timer_entries``) or the run table (``gpu.timer_runs`` pending Schedules) lacks
+        room.  Time is explicit: the clock counts ticks and only ``Tick()`` moves it.  Routing
+        happens when a message is due, not now.  It reads its counts on the host (refused
+        under graph capture).  The queue is per runtime, like the dead-letter queue."""
+        if self._rt is None:
+            raise RuntimeError("Client.Schedule needs the cluster's device runtime (Join with a gpu: section)")
+        return self._rt.schedule(batch, delay, self._dead_letter_tag() if tag is None else int(tag))
+
+    def Tick(self, ticks: int | None = None, **kw):
+        """Advance the runtime's clock by one tick and send the messages that are due, in
+        ticket order, as one batch through ``Send`` with every keyword it takes (``retries``,
+        ``coalesce``, ``cache``, ``breaker``, ``limit``, ``dead_letter``, ``gather``, ``account``).
+        Returns an ``ops.timers.Ticked``: ``due`` (the records: ``ticket``, ``row``, ``actor``,
+        ``method``, ``delay``, ``t0``, ``a0``, ``a1``, ``a2``, ``tag``, ``n``, ``torn``), ``value``,
+        ``status``.  The queue is per runtime and the tag is not filtered on: ``Tick`` sends
+        whatever is due -- other clients' messages included -- to this client's own service.
+        The keywords are checked before the clock moves.  ``ticks=n``: ``n`` single ticks, a
+        list.  It reads ``n_due`` on the host (refused under graph capture) and is a collective
+        Send at world > 1."""
+        if self._rt is None:
+            raise RuntimeError("Client.Tick needs the cluster's device runtime (Join with a gpu: section)")
+        if kw.get("dead_letter") is not False:
+            kw.setdefault("dead_letter_tag", self._dead_letter_tag())
+        return self._rt.tick(self.service, router=self._replica_router(), ticks=ticks, **kw)
+
+    def Timers(self) -> dict:
+        """The timer queue's counters: ``now``, ``head``, ``tail``, ``live``, ``runs``, ``refused``,
+        ``delivered``, ``full``, ``torn`` and its sizes (one host read);
+        ``Stats()["runtime"]["timers"]`` has the same."""
+        if self._rt is None:
+            raise RuntimeError("Client.Timers needs the cluster's device runtime (Join with a gpu: section)")
+        return self._rt.timers()
+
     def Ask(self, questions, scatter, op: str = "sum", sentinel=None, **kw):
         """Scatter-gather on the device: the optimus coordinator's ``splitWork`` ..
         ``watchReplies`` (coordinator.go:67-98) for any rule and op.  ``scatter`` -- an
@@ -542,6 +583,7 @@ class Client:
 
     call, go, send, tell, close, flush, ask = Call, Go, Send, Tell, Close, Flush, Ask
     dead_letters, redrive = DeadLetters, Redrive
+    schedule, tick, timers = Schedule, Tick, Timers
     subscribe, unsubscribe, topics, publish = Subscribe, Unsubscribe, Topics, Publish
 
     @property

@@ -349,6 +349,10 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("dead_letters", &GpuConfig::dead_letters)
       .def_readwrite("dead_letter_entries", &GpuConfig::dead_letter_entries)
       .def_readwrite("dead_letter_mask", &GpuConfig::dead_letter_mask)
+      .def_readwrite("timers", &GpuConfig::timers)
+      .def_readwrite("timer_entries", &GpuConfig::timer_entries)
+      .def_readwrite("timer_horizon", &GpuConfig::timer_horizon)
+      .def_readwrite("timer_runs", &GpuConfig::timer_runs)
       .def_readwrite("topics", &GpuConfig::topics)
       .def_readwrite("elastic", &GpuConfig::elastic)
       .def_readwrite("delivery", &GpuConfig::delivery)

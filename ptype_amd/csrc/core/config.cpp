@@ -182,6 +182,25 @@ void decode_ptype(const YNode& root, Config& c) {
             fail(Errc::kConfig, "gpu.dead_letter_mask must be in [2, 2^32) with bit 0 (STATUS_OK) clear");
           c.gpu.dead_letter_mask = (uint64_t)n;
         }
+        else if (g.first == "timers") c.gpu.timers = want_bool(G, g.first, g.second);
+        else if (g.first == "timer_entries") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 64 || n > (1ll << 24) || (n & (n - 1)))
+            fail(Errc::kConfig, "gpu.timer_entries must be a power of two in [64, 2^24]");
+          c.gpu.timer_entries = (uint64_t)n;
+        }
+        else if (g.first == "timer_horizon") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 16 || n > 1024 || (n & (n - 1)))
+            fail(Errc::kConfig, "gpu.timer_horizon must be a power of two in [16, 1024]");
+          c.gpu.timer_horizon = (uint32_t)n;
+        }
+        else if (g.first == "timer_runs") {
+          const int64_t n = want_int(G, g.first, g.second);
+          if (n < 4 || n > 4096 || (n & (n - 1)))
+            fail(Errc::kConfig, "gpu.timer_runs must be a power of two in [4, 4096]");
+          c.gpu.timer_runs = (uint32_t)n;
+        }
         else if (g.first == "topics") {
           const int64_t n = want_int(G, g.first, g.second);
           if (n < 1 || n > (1ll << 20)) fail(Errc::kConfig, "gpu.topics must be in [1, 2^20]");

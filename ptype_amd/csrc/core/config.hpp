@@ -77,6 +77,10 @@ struct GpuConfig {
   bool dead_letters = false;  // Send files its failed calls in the HBM dead-letter queue by default (ops/dead_letters.py)
   uint64_t dead_letter_entries = 1 << 16;  // ring records (64 B each; a power of two in [64, 2^24])
   uint64_t dead_letter_mask = 0;  // statuses that make a dead letter, bit s = status s (0: statuses 1 to 6)
+  bool timers = false;  // the runtime keeps a timer queue in HBM: Client.Schedule / Client.Tick (ops/timers.py)
+  uint64_t timer_entries = 1 << 20;  // ring records (64 B each; a power of two in [64, 2^24])
+  uint32_t timer_horizon = 256;      // the largest delay in ticks (a power of two in [16, 1024])
+  uint32_t timer_runs = 256;         // Schedules that may be pending at once (a power of two in [4, 4096])
   uint64_t topics = 1024;  // pub/sub topic ids of the service: [0, topics) (ops/topics.py; [1, 2^20])
   // rank failures (runtime.py recover): Join's group re-forms through the store
   bool elastic = true;          // recover a failed Send (abort, re-form, re-home, re-send)

@@ -17,6 +17,7 @@
 #include "gather.hpp"
 #include "scatter.hpp"
 #include "dead_letters.hpp"
+#include "timers.hpp"
 #include "ledger.hpp"
 #include "limit.hpp"
 #include "mailbox.hpp"
@@ -119,6 +120,16 @@ void launch_dlq_append(uintptr_t, int64_t, uint32_t, uintptr_t, uintptr_t, uint3
                        uintptr_t, int64_t, uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t);
 void launch_dlq_take(uintptr_t, uintptr_t, int64_t, int64_t, int64_t, bool, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                      uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t);
+int64_t timer_tile();
+void launch_timer_count(uintptr_t, int64_t, int64_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int64_t, uintptr_t,
+                        uintptr_t);
+void launch_timer_file(uintptr_t, int64_t, int64_t, uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t,
+                       int64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, int64_t, uintptr_t,
+                       int64_t, uintptr_t, uintptr_t);
+void launch_timer_due(uintptr_t, uintptr_t, uintptr_t, int64_t, int64_t, uintptr_t, uintptr_t, bool, uintptr_t);
+void launch_timer_take(uintptr_t, uintptr_t, int64_t, uintptr_t, uintptr_t, int64_t, int64_t, int64_t, uintptr_t,
+                       uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                       uintptr_t, uintptr_t);
 int64_t coalesce_tile();
 void launch_coalesce_group(uintptr_t, uintptr_t, uint32_t, uintptr_t, uintptr_t, uintptr_t, int64_t, uintptr_t, int,
                            uintptr_t, uintptr_t);
@@ -439,6 +450,79 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("attempts"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("tag"), py::arg("stream"),
         "n letters from ticket t0 into SoA columns; mismatching ticket words counted in the control line's torn; "
         "drain: tail = t0 + n");
+
+  // ---- timer queue (timers.hip, timers.hpp): delayed messages in an HBM ring, Schedule and Tick
+  m.def("timer_layout", []() {
+    py::dict rec, hdr, ctl, scr, d;
+    rec["ticket"] = kTmrTicket;
+    rec["due"] = kTmrDue;
+    rec["row_delay"] = kTmrRowDelay;
+    rec["actor_method"] = kTmrActorMethod;
+    rec["a0"] = kTmrA0;
+    rec["a1"] = kTmrA1;
+    rec["a2"] = kTmrA2;
+    rec["tag"] = kTmrTag;
+    hdr["t0"] = kTmrT0;
+    hdr["base"] = kTmrBase;
+    hdr["n"] = kTmrN;
+    hdr["max_delay"] = kTmrMaxDelay;
+    hdr["seq"] = kTmrSeq;
+    ctl["now"] = kTmrNow;
+    ctl["head"] = kTmrHead;
+    ctl["tail"] = kTmrTail;
+    ctl["runs_head"] = kTmrRunsHead;
+    ctl["runs_tail"] = kTmrRunsTail;
+    ctl["refused"] = kTmrRefused;
+    ctl["delivered"] = kTmrDelivered;
+    ctl["torn"] = kTmrTorn;
+    scr["k"] = kTmrSK;
+    scr["refused"] = kTmrSRefused;
+    scr["max_delay"] = kTmrSMaxDelay;
+    scr["head"] = kTmrSHead;
+    scr["runs_head"] = kTmrSRunsHead;
+    scr["now"] = kTmrSNow;
+    scr["n_due"] = kTmrSDue;
+    scr["segs"] = kTmrSSegs;
+    d["record"] = rec;
+    d["header"] = hdr;
+    d["control"] = ctl;
+    d["scratch"] = scr;
+    d["record_words"] = kTmrRecordWords;
+    d["header_words"] = kTmrHeaderWords;
+    d["control_words"] = kTmrCtrlWords;
+    d["scratch_words"] = kTmrScratchWords;
+    d["tile"] = timer_tile();
+    d["min_entries"] = kTmrMinEntries;
+    d["max_entries"] = kTmrMaxEntries;
+    d["min_horizon"] = kTmrMinHorizon;
+    d["max_horizon"] = kTmrMaxHorizon;
+    d["min_runs"] = kTmrMinRuns;
+    d["max_runs"] = kTmrMaxRuns;
+    return d;
+  }, "u64 word indices of a timer record, a run descriptor's header, the control and the scratch line (timers.hpp), "
+     "and the sizes");
+  m.def("timer_desc_words", [](int64_t horizon) { return timer_desc_words(horizon); }, py::arg("horizon"),
+        "u64 words of one run descriptor: the header and off[horizon + 2] u32 padded to 64 B");
+  m.def("timer_count", &launch_timer_count, py::arg("delay"), py::arg("uniform"), py::arg("M"), py::arg("ctrl"),
+        py::arg("scratch"), py::arg("horizon"), py::arg("hist"), py::arg("hist_words"), py::arg("off"),
+        py::arg("stream"),
+        "launches 1 and 2 of a Schedule: per-tile histograms of the delay column (0: every row has the delay uniform), "
+        "their prefixes and off[] into workspace, K / refused / max_delay and the control words found into scratch");
+  m.def("timer_file", &launch_timer_file, py::arg("delay"), py::arg("uniform"), py::arg("M"), py::arg("actor"),
+        py::arg("method_col"), py::arg("method_uniform"), py::arg("a0"), py::arg("a1"), py::arg("a2"), py::arg("tag"),
+        py::arg("ring"), py::arg("runs"), py::arg("ctrl"), py::arg("scratch"), py::arg("entries"), py::arg("horizon"),
+        py::arg("n_runs"), py::arg("hist"), py::arg("hist_words"), py::arg("off"), py::arg("stream"),
+        "launch 3 of a Schedule, after the host found room: the accepted rows into the ring sorted by (delay, row), the "
+        "run's descriptor, head / runs_head / refused committed");
+  m.def("timer_due", &launch_timer_due, py::arg("runs"), py::arg("ctrl"), py::arg("scratch"), py::arg("horizon"),
+        py::arg("n_runs"), py::arg("seg_first"), py::arg("seg_ticket"), py::arg("commit"), py::arg("stream"),
+        "one tick: the live runs' due segments into the workspace, n_due and segs into scratch; with commit the clock, "
+        "delivered and both tails move");
+  m.def("timer_take", &launch_timer_take, py::arg("ring"), py::arg("ctrl"), py::arg("entries"), py::arg("seg_first"),
+        py::arg("seg_ticket"), py::arg("segs"), py::arg("n_runs"), py::arg("n"), py::arg("ticket"), py::arg("row"),
+        py::arg("actor"), py::arg("method"), py::arg("delay"), py::arg("t0"), py::arg("a0"), py::arg("a1"),
+        py::arg("a2"), py::arg("tag"), py::arg("stream"),
+        "the n due records of the last timer_due into SoA columns, in ticket order per run and run order");
 
   // ---- Send coalescing (coalesce.hip, coalesce.hpp): duplicates of a pure call are sent once
   m.def("coalesce_tile", &coalesce_tile, "messages per block of coalesce_group's insert kernel");

@@ -76,7 +76,9 @@ class DeviceRuntime:
                  breaker: bool = False, breaker_threshold: int = 5, breaker_cooldown: int = 8,
                  breaker_actors: int = 0, breaker_trip_on=None, limit: bool = False, limit_rate: int = 1,
                  limit_burst: int = 1, limit_actors: int = 0, dead_letters: bool = False,
-                 dead_letter_entries: int = 1 << 16, dead_letter_mask=None, max_topics: int = 1024):
+                 dead_letter_entries: int = 1 << 16, dead_letter_mask=None, max_topics: int = 1024,
+                 timers: bool = False, timer_entries: int = 1 << 20, timer_horizon: int = 256,
+                 timer_runs: int = 256):
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -188,6 +190,16 @@ class DeviceRuntime:
         if dead_letters:
             self._dlq = DL.DeadLetters(self.device, self.dead_letter_entries, self.dead_letter_mask,
                                        max_rows=self.max_batch)
+        # Timer queue (ops/timers.py, opt-in): delayed messages kept whole in an HBM ring until
+        # their tick (schedule(), tick()); the clock counts ticks, there is no wall clock
+        from .ops import timers as TM
+
+        self.timer_entries, self.timer_horizon = TM.check_entries(timer_entries), TM.check_horizon(timer_horizon)
+        self.timer_runs = TM.check_runs(timer_runs)
+        self._timers = None
+        if timers:
+            self._timers = TM.TimerQueue(self.device, self.timer_entries, self.timer_horizon, self.timer_runs,
+                                         max_rows=self.max_batch)
         # Scatter-gather (ask, ops/scatter.py): host counters, from what every expansion read
         self._scatter_counters = {"asks": 0, "questions": 0, "rows": 0, "oob": 0}
         # Pub/sub topics (publish, ops/topics.py): per service the follower-fed table and its scatter,
@@ -267,7 +279,8 @@ class DeviceRuntime:
                  breaker_actors=g.breaker_actors, limit=g.limit, limit_rate=g.limit_rate,
                  limit_burst=g.limit_burst, limit_actors=g.limit_actors, dead_letters=g.dead_letters,
                  dead_letter_entries=g.dead_letter_entries, dead_letter_mask=g.dead_letter_mask or None,
-                 max_topics=g.topics)
+                 max_topics=g.topics, timers=g.timers, timer_entries=g.timer_entries,
+                 timer_horizon=g.timer_horizon, timer_runs=g.timer_runs)
         rt._tcp_store, rt._owns_group = tcp, owns
         rt._addr = (core_cluster.local_addr, int(cfg.port))
         if members is not None and g.elastic:
@@ -670,10 +683,7 @@ class DeviceRuntime:
         Send raises later than that (letters of an ordered method re-sent with ``retries``,
         a rank failure that is not recovered) finds the letters already taken: they are not
         put back."""
-        import inspect
-
         from .ops.dead_letters import Redrive
-        from .ops.retry import retry_mask
 
         if self._dlq is None:
             raise ValueError("redrive(): this runtime keeps no dead-letter queue "
@@ -684,20 +694,7 @@ class DeviceRuntime:
                 self.on_gpu and torch.cuda.is_current_stream_capturing()):
             raise ValueError("redrive inside a captured Send: the queue's head and tail are read on the host")
         # what send would refuse, before a letter leaves the queue
-        inspect.signature(self.send).bind(service, None, router=router, **send_kw)  # (an unknown keyword: TypeError)
-        if send_kw.get("account") and self.ledger is None:
-            raise ValueError("redrive(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
-                             "gpu.ledger)")
-        if send_kw.get("retries"):
-            if int(send_kw["retries"]) < 0:
-                raise ValueError("retries >= 0")
-            if not send_kw.get("resend_overflow", True):
-                raise ValueError("redrive(retries > 0) runs after the overflow re-sends: resend_overflow=False "
-                                 "excludes it")
-            if send_kw.get("retry_on") is not None:
-                retry_mask(send_kw["retry_on"])
-        if router is None:
-            self._check_service(service)
+        self._check_send_keywords("redrive", service, router, send_kw)
         ex = self.exchange
         n = min(self._dlq.read()["unread"], ex.max_chunk * ex.chunks)
         if max_letters is not None:
@@ -714,6 +711,119 @@ class DeviceRuntime:
             out = (torch.empty(0, dtype=torch.int64, device=self.device),
                    torch.empty(0, dtype=torch.int32, device=self.device))
         return Redrive(letters, out[0], out[1])
+
+    def _check_send_keywords(self, who: str, service: str | None, router, send_kw: dict) -> None:
+        """What ``send`` would refuse whatever the batch, raised before ``who`` (redrive, tick)
+        takes anything out of its queue: an unknown keyword (TypeError), ``account=True``
+        without a ledger, ``retries`` with ``resend_overflow=False`` or a bad ``retry_on``, a
+        service this runtime does not host."""
+        import inspect
+
+        from .ops.retry import retry_mask
+
+        inspect.signature(self.send).bind(service, None, router=router, **send_kw)  # (an unknown keyword: TypeError)
+        if send_kw.get("account") and self.ledger is None:
+            raise ValueError(f"{who}(account=True): this runtime keeps no Send ledger (DeviceRuntime(ledger=True), "
+                             "gpu.ledger)")
+        if send_kw.get("retries"):
+            if int(send_kw["retries"]) < 0:
+                raise ValueError("retries >= 0")
+            if not send_kw.get("resend_overflow", True):
+                raise ValueError(f"{who}(retries > 0) runs after the overflow re-sends: resend_overflow=False "
+                                 "excludes it")
+            if send_kw.get("retry_on") is not None:
+                retry_mask(send_kw["retry_on"])
+        if router is None:
+            self._check_service(service)
+
+    def _timer_queue(self, who: str):
+        if self._timers is None:
+            raise ValueError(f"{who}: this runtime keeps no timer queue (DeviceRuntime(timers=True), gpu.timers)")
+        if (self._exchange is not None and self._exchange._capturing) or (
+                self.on_gpu and torch.cuda.is_current_stream_capturing()):
+            raise ValueError(f"{who} inside a captured Send: the timer queue's counts are read on the host")
+        return self._timers
+
+    def schedule(self, batch: B.MsgBatch, delay, tag: int = 0):
+        """Delayed messages (Akka's ``scheduleOnce``, protoactor's ``SendOnce``, SQS
+        ``DelaySeconds``): row ``i`` of ``batch`` is filed in the runtime's timer queue in HBM
+        (ops/timers.py), with its whole call under the id its caller wrote and ``tag``, to be
+        sent by the ``tick()`` ``delay[i]`` ticks from now.  ``delay``: an int, or an int32[M]
+        column on the batch's device; a row whose delay is outside ``[1, timer_horizon]`` is
+        not filed and counted in ``refused``.  Nothing is routed now: the replica round robin
+        and a re-homed actor are resolved when the message is due.  Returns an
+        ``ops.timers.Scheduled`` (``n``, ``refused``, ``first_ticket``, ``now``); raises
+        ``ops.timers.TimerQueueFull``, with nothing filed, when the ring or the run table lacks
+        room.  It reads its counts on the host, so it is refused under graph capture; it is
+        the caller's view (no collective)."""
+        return self._timer_queue("schedule").schedule(batch, delay, tag)
+
+    def tick(self, service: str | None, router=None, ticks: int | None = None, **send_kw):
+        """Advance the runtime's clock by one tick and send what is due: the due records of
+        every pending Schedule, in ticket order (per Schedule by ``(delay, row)``, Schedules in
+        call order -- two messages for one actor due at the same tick are in that order in the
+        batch, so with ``delivery="mailbox"`` an ordered method keeps its per-actor FIFO; the due
+        batch carries a method column, and on the direct path an ordered method's updates are
+        serialised per actor but not in batch order), go through ``send`` as one batch of the
+        logical ids their callers wrote, with every keyword it takes (``send_kw``).  Returns an
+        ``ops.timers.Ticked``: the ``due`` records (``ops.timers.Timers``) and the Send's ``(value,
+        status)``, row for row.  More due rows than one Send holds are sent as consecutive
+        slices in ticket order and the replies concatenated (a ``gather`` spans the whole tick
+        and refuses that).  At world > 1 a tick is a collective Send like any other: a rank
+        with nothing due joins with an empty batch, and every rank must send the same number
+        of slices; at world 1 with nothing due the Send is skipped.  ``ticks=n`` is a host loop
+        of ``n`` single ticks and returns their list.  The keywords are checked before the
+        clock moves -- an unknown one, ``account=True`` without a ledger, ``dead_letter=True``
+        without a queue, a ``gather`` of another size than what is due, ``retries`` with
+        ``resend_overflow=False`` or a bad ``retry_on``, a service this runtime does not host
+        -- so such a call leaves the clock and the queue as they were.  An error the Send
+        raises later than that finds the records taken: they are not put back.  It reads
+        ``n_due`` on the host, so it is refused under graph capture."""
+        from .ops.timers import Ticked
+
+        tq = self._timer_queue("tick")
+        if "dead_letter_attempts" in send_kw:
+            raise ValueError("tick: the rows that will be due are not the caller's to count attempts for")
+        self._check_send_keywords("tick", service, router, send_kw)
+        self._dead_letter_sink(send_kw.get("dead_letter"))  # (dead_letter=True without a queue: ValueError)
+        if ticks is not None:
+            if int(ticks) < 0 or send_kw.get("gather") is not None:
+                raise ValueError("tick(ticks=n): n >= 0, and a gather belongs to one tick")
+            return [self.tick(service, router=router, **send_kw) for _ in range(int(ticks))]
+        ex = self.exchange
+        cap = ex.max_chunk * ex.chunks
+        if send_kw.get("gather") is not None:
+            n = tq.peek()
+            send_kw["gather"].check_batch(n)
+            if n > cap:
+                raise ValueError(f"tick(gather=): {n} rows are due, more than one Send holds ({cap})")
+        due = tq.tick()
+        outs = [self.send(service, self._timer_slice(due, lo, min(lo + cap, due.n)), router=router, **send_kw)
+                for lo in range(0, due.n, cap)]
+        if not outs and self.world > 1:
+            outs = [self.send(service, due.batch(), router=router, **send_kw)]
+        if len(outs) == 1:
+            return Ticked(due, outs[0][0], outs[0][1])
+        if not outs:
+            return Ticked(due, torch.empty(0, dtype=torch.int64, device=self.device),
+                          torch.empty(0, dtype=torch.int32, device=self.device))
+        return Ticked(due, torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]))
+
+    @staticmethod
+    def _timer_slice(due, lo: int, hi: int) -> B.MsgBatch:
+        if lo == 0 and hi == due.n:
+            return due.batch()
+        # (copies: a Send's kernels load their columns from allocation-aligned tensors)
+        return B.MsgBatch(*(c[lo:hi].clone() for c in (due.actor, due.a0, due.a1, due.a2, due.method)))
+
+    def timers(self) -> dict:
+        """The timer queue's counters (one host read of its control line): ``now``, ``head``,
+        ``tail``, ``live`` (records filed and not yet due), ``runs`` (pending Schedules),
+        ``refused``, ``delivered``, ``full`` (Schedules refused with ``TimerQueueFull``), ``torn`` and
+        the sizes ``entries``, ``horizon``, ``max_runs``."""
+        if self._timers is None:
+            raise ValueError("timers(): this runtime keeps no timer queue (DeviceRuntime(timers=True), gpu.timers)")
+        return self._timers.read()
 
     def ask(self, service: str | None, questions: B.MsgBatch, scatter, op: str = "sum", sentinel=None, key=None,
             **send_kw):
@@ -1311,6 +1421,9 @@ class DeviceRuntime:
         out["dead_letters"] = (self._dlq.read() if self._dlq is not None  # (one host read of the control line)
                                else {"entries": 0, "appended": 0, "unread": 0, "dropped": 0, "sends": 0, "torn": 0,
                                      "redrives": 0, "redriven": 0})
+        out["timers"] = (self._timers.read() if self._timers is not None  # (one host read of the control line)
+                         else {"now": 0, "head": 0, "tail": 0, "live": 0, "runs": 0, "refused": 0, "delivered": 0,
+                               "full": 0, "torn": 0, "entries": 0, "horizon": 0, "max_runs": 0})
         return out
 
     def close(self) -> None:
