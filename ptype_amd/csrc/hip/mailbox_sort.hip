@@ -317,6 +317,16 @@ __global__ __launch_bounds__(kST) void mbx_onesweep_kernel(SortIn in, MboxView m
 // word a wave sets before the first barrier when a lane spills, read behind it, cleared
 // behind the second (in place of __syncthreads_or: three barriers around an LDS word).
 //
+// The front half of a tile (profiles/rank_scan.md): the kernel is bound by instruction issue, not
+// by memory, so resolve and rank are written for their instruction counts.  resolve_pres_lean
+// turns the actor ids into mailboxes in place -- eight presence words read back to back, one
+// wait, no branch; the hash-table probes behind one wave-uniform test -- and marks every message
+// that takes no slot with kNoSlot, so no rank array exists.  os_rank_scan (a view has at most
+// kStatelessShards shards here) ranks by one-hot byte counters scanned across the wave with DPP
+// adds and keeps the wave's running counts in a register: one ds_bpermute per item and one LDS
+// write of the row per tile, which therefore needs no clearing.  The field maxima are reduced by
+// DPP as well (wave_max_u32).
+//
 // Tiles: no counter, no flag, no block waits for another.  Block b of G (a multiple of 8
 // where there are 8 or more) sits on XCD b % 8; with a tile count that is a multiple of 8
 // it takes tiles x * T/8 + j, j = b / 8 + i * G/8 -- the XCD virt_block gives each tile in
@@ -366,7 +376,6 @@ void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx
   }
   if (threadIdx.x < 3) tmax[threadIdx.x] = 0;
   if (threadIdx.x < 2) vote[threadIdx.x] = 0;
-  for (uint32_t s = lane; s < S; s += kWave) wcnt2[w * S + s] = 0;
   __syncthreads();
   const uint32_t w8 = in.rec8 ? *in.r8w : 0u;
   const bool maxima = in.rec8 || in.recw;
@@ -380,15 +389,13 @@ void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx
   int64_t v0[SK], v1[SK];  // the coming tile's arguments, in flight from behind the last tile's stores
   PackedRanks<SK> wrp;
   {
-    uint32_t a[SK], wr[SK];
-    int r[SK];
+    uint32_t wr[SK];
     const bool full = tile_is_full<SK>(in, first);
-    load_actors<SK>(in, first, a);
+    load_actors<SK>(in, first, nx);
     load_args_tile<SK>(in, first, full, v0, v1);
-    os_resolve<4, SK>(in, lpres, a, r, nx);
-    os_rank<SK>(in, mv.log_s, first, r, nx, wcnt2 + w * S, wr);
-#pragma unroll
-    for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+    resolve_pres_lean<SK>(in, lpres, nx);
+    os_rank_scan<SK>(S, nx, wcnt2 + w * S, wr);
+    wrp.pack(wr);
   }
   __syncthreads();
   // (S <= kST: a shard's thread keeps its run's count and reserved offset in registers)
@@ -474,15 +481,10 @@ void mbx_persist_sort_kernel(SortIn in, MboxView mv, uint32_t* __restrict__ sidx
       load_args_tile<SK>(in, t + stride, full_next, v0, v1);
       // the next tile in the other buffer (last read before this tile's barrier): resolved, ranked, reserved
       uint32_t* wnext = wcnt2 + (b ^ 1) * (kST / kWave) * S;
-      for (uint32_t s = lane; s < S; s += kWave) wnext[w * S + s] = 0;
-      uint32_t a[SK], wr[SK];
-      int r[SK];
-#pragma unroll
-      for (int k = 0; k < SK; ++k) a[k] = nx[k];
-      os_resolve<4, SK>(in, lpres, a, r, nx);
-      os_rank<SK>(in, mv.log_s, t + stride, r, nx, wnext + w * S, wr);
-#pragma unroll
-      for (int k = 0; k < SK / 2; ++k) wrp.p[k] = wr[2 * k] | (wr[2 * k + 1] << 16);
+      uint32_t wr[SK];
+      resolve_pres_lean<SK>(in, lpres, nx);
+      os_rank_scan<SK>(S, nx, wnext + w * S, wr);
+      wrp.pack(wr);
       __syncthreads();
       // (every thread has read this tile's flag word: cleared for the tile after the next, whose votes
       // follow the next tile's barrier)

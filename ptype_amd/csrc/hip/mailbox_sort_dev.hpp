@@ -103,9 +103,24 @@ __device__ __forceinline__ void load_args_tile(const SortIn& in, uint32_t t, boo
 }
 
 __device__ __forceinline__ uint32_t bitlen64(uint64_t x) { return x ? 64u - (uint32_t)__clzll(x) : 0u; }
+// One DPP step of a wave scan or reduction: lane l's source lane's `v` (CTRL: 0x111.. row_shr:1..,
+// 0x142 row_bcast:15, 0x143 row_bcast:31), 0 where the lane has no source or its row is not in ROWS.
+// The compiler folds the step into the add / max that takes it (v_add_u32_dpp, v_max_u32_dpp).
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ uint32_t dpp_step(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
+}
+// The wave's maximum (wave-uniform): an inclusive max-scan in VALU -- four row shifts, then lane 15
+// of rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 and 3 -- read from lane 63.  No trip through
+// the LDS pipe (six dependent ds_bpermute, each waited for, before).
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-  return v;
+  v = max(v, dpp_step<0x111>(v));
+  v = max(v, dpp_step<0x112>(v));
+  v = max(v, dpp_step<0x114>(v));
+  v = max(v, dpp_step<0x118>(v));
+  v = max(v, dpp_step<0x142, 0xa>(v));
+  v = max(v, dpp_step<0x143, 0xc>(v));
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, kWave - 1);
 }
 
 // The next Send's 8-B field widths from this Send's per-tile bit lengths (the last
@@ -177,6 +192,55 @@ __device__ __forceinline__ void resolve_pres(const SortIn& in, const uint32_t* l
   }
 }
 
+// The persistent sort's form of resolve_pres, in place: the tile's actor ids `am` become its
+// mailboxes, kNoSlot for a message of another rank, without an actor (past the batch too:
+// load_actors gives those 0xffffffff) or with a mailbox past kMaxMbox -- what os_rank would make of
+// resolve_pres' (rank, mailbox), so no rank array crosses to the ranking.  The tile's presence
+// words are read back to back and classified behind one wait in straight-line code: no branch and
+// no LDS latency per item.  An id past the directory reads as state 2 (probe).  The hash-table
+// probes -- state 2 on any id but 0xffffffff -- sit behind one wave-uniform test that a wave of
+// directory ids never passes; there a lane finds its items again and probes them one at a time
+// through ONE inlined lookup_entry (picked and put back by compares), so the fast path carries no
+// copies of the arrays and the kernel one probe loop instead of sixteen.
+__device__ __forceinline__ uint32_t pres_state(uint32_t n_dir, uint32_t id, uint32_t word) {
+  // (v_bfe_u32 takes the low five bits of its offset: id's place in its word needs no mask)
+  return __builtin_amdgcn_ubfe(id < n_dir ? word : 0xaaaaaaaau, id << 1, 2u);
+}
+template <int SK>
+__device__ __forceinline__ void resolve_pres_lean(const SortIn& in, const uint32_t* lpres, uint32_t (&am)[SK]) {
+  uint32_t pw[SK];
+#pragma unroll
+  for (int k = 0; k < SK; ++k) pw[k] = lpres[(am[k] < in.n_dir ? am[k] : 0u) >> 4];  // (word 0: inside the staged map)
+  bool probes = false;
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t st = pres_state(in.n_dir, am[k], pw[k]);
+    probes |= st == 2 && am[k] != 0xffffffffu;
+    am[k] = st == 0 ? kNoSlot : am[k];  // (state 1: a directory id is its own mailbox, below kPresMax)
+  }
+  if (__any(probes)) {
+    uint32_t todo = 0;  // this lane's items that need the hash table
+#pragma unroll
+    for (int k = 0; k < SK; ++k) {
+      const uint32_t st = pres_state(in.n_dir, am[k], lpres[(am[k] < in.n_dir ? am[k] : 0u) >> 4]);
+      todo |= st == 2 && am[k] != 0xffffffffu ? 1u << k : 0u;
+    }
+    while (todo != 0) {
+      const int k = __builtin_ctz(todo);
+      todo &= todo - 1;
+      uint32_t id = am[0];
+#pragma unroll
+      for (int j = 1; j < SK; ++j) id = j == k ? am[j] : id;
+      int rr;
+      uint32_t mm;
+      lookup_entry(in.table, in.mask, actor_key(id), rr, mm);
+      mm = rr == in.rank_self && mm < kMaxMbox ? mm : kNoSlot;
+#pragma unroll
+      for (int j = 0; j < SK; ++j) am[j] = j == k ? mm : am[j];
+    }
+  }
+}
+
 // ---- the phases of a one-pass tile, shared by onesweep_tile (one tile per block) and the
 // persistent reserving sort (mbx_persist_sort_kernel: a block walks several tiles)
 //
@@ -210,6 +274,45 @@ __device__ __forceinline__ void os_rank(const SortIn& in, uint32_t log_s, uint32
     }
     wr[k] = (unsigned)__shfl((int)old, leader) + below;
   }
+}
+
+// Phase 2 for a view of at most kStatelessShards (8) shards, with os_rank's results: the ranks
+// by a scan instead of a match per shard bit and a leader lane's read-modify-write of the LDS row.
+// Per item a lane sets a one-hot BYTE counter -- byte sh of a 64-bit word, its low dword for
+// shards 0..3 and its high dword for shards 4..7 -- and both dwords are inclusive-scanned across
+// the wave by DPP adds (a field reaches 64 at most: no carry leaves a byte).  A lane's own byte,
+// less one, is its rank among the item's earlier lanes of its shard; lane 63 holds the item's
+// totals.  The wave's running count of shard s stays in lane s of one register (`run`): a lane's
+// base is that register read at lane sh before the item's totals are added, and the row of counts
+// goes to LDS once per tile, from lanes < S (`wrow` needs no clearing).
+// `mb` comes from resolve_pres_lean: kNoSlot marks a message that takes no slot (no bounds test
+// here: a message past the batch is among them).
+template <int SK>
+__device__ __forceinline__ void os_rank_scan(uint32_t S, const uint32_t (&mb)[SK], uint32_t* wrow, uint32_t (&wr)[SK]) {
+  static_assert(kStatelessShards == 8, "one byte per shard in two dwords");
+  const uint32_t lane = lane_id();
+  const uint32_t lsh = (lane & 7u) * 8u;  // (lanes 0..7) the lane's shard's byte in the totals
+  uint32_t run = 0;
+#pragma unroll
+  for (int k = 0; k < SK; ++k) {
+    const uint32_t sh = mb[k] & (S - 1);
+    const uint64_t hot = (uint64_t)(mb[k] != kNoSlot ? 1u : 0u) << (sh * 8u);
+    uint32_t lo = (uint32_t)hot, hi = (uint32_t)(hot >> 32);
+    lo += dpp_step<0x111>(lo), hi += dpp_step<0x111>(hi);
+    lo += dpp_step<0x112>(lo), hi += dpp_step<0x112>(hi);
+    lo += dpp_step<0x114>(lo), hi += dpp_step<0x114>(hi);
+    lo += dpp_step<0x118>(lo), hi += dpp_step<0x118>(hi);
+    lo += dpp_step<0x142, 0xa>(lo), hi += dpp_step<0x142, 0xa>(hi);
+    lo += dpp_step<0x143, 0xc>(lo), hi += dpp_step<0x143, 0xc>(hi);
+    // (inclusive: a message counts itself; one without a slot leaves with a rank nobody reads)
+    const uint32_t below = (((sh & 4u) ? hi : lo) >> ((sh & 3u) * 8u)) & 0xffu;
+    const uint32_t base = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sh << 2), (int)run);
+    wr[k] = base + below - 1u;
+    const uint64_t tot = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, kWave - 1) << 32) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)lo, kWave - 1);
+    run += (uint32_t)(tot >> lsh) & 0xffu;
+  }
+  if (lane < S) wrow[lane] = run;
 }
 
 // Phase 3, per shard (one thread each): the wave counts turned into wave offsets (returns
@@ -299,6 +402,11 @@ __device__ __forceinline__ void os_loads_in(const int64_t (&v0)[SK], const int64
 template <int SK>
 struct PackedRanks {
   uint32_t p[SK / 2];
+  // (the low halves of a pair, by one byte permute: a message without a slot may carry any rank)
+  __device__ __forceinline__ void pack(const uint32_t (&wr)[SK]) {
+#pragma unroll
+    for (int k = 0; k < SK / 2; ++k) p[k] = __builtin_amdgcn_perm(wr[2 * k + 1], wr[2 * k], 0x05040100u);
+  }
   __device__ __forceinline__ uint32_t operator[](int k) const { return (p[k >> 1] >> ((k & 1) * 16)) & 0xffffu; }
 };
 
