@@ -216,7 +216,9 @@ __device__ __forceinline__ ReplyRecord run_handler(const MsgRecord& m, int64_t* 
           if (ob.cap) {
             const uint64_t stride = (uint64_t)m.a2 & 0xffffffffull, n = (uint64_t)m.a2 >> 32;
             const uint64_t next = n ? ((uint64_t)m.a0 + stride) % n : (uint64_t)m.a0;
-            outbox_emit(ob, (uint32_t)m.a0, kForward, (int64_t)next, m.a1 - 1, m.a2);
+            // a hop outside the id space names no actor (0xffffffff), never the actor its low 32 bits spell
+            const uint32_t to = (uint64_t)m.a0 < 0xffffffffull ? (uint32_t)m.a0 : 0xffffffffu;
+            outbox_emit(ob, to, kForward, (int64_t)next, m.a1 - 1, m.a2);
           } else {
             r.status = kStatusFailed;  // no outbox bound: the send cannot happen
           }

@@ -382,10 +382,17 @@ def _handler_ref(method, actor, a0, a1, a2, state, outbox=None):
             if outbox is None:
                 status[i] = STATUS_FAILED
                 continue
-            w = int(a2[i]) & 0xFFFFFFFFFFFFFFFF
+            # u64 wrapping arithmetic, as the device's; a hop outside the id space goes to the
+            # actor field that names no actor, never to the actor its low 32 bits spell
+            u64 = 0xFFFFFFFFFFFFFFFF
+            w, hop = int(a2[i]) & u64, int(a0[i])
             stride, n = w & 0xFFFFFFFF, w >> 32
-            nxt = (int(a0[i]) + stride) % n if n else int(a0[i])
-            outbox.emit_cpu(int(a0[i]) & 0xFFFFFFFF, FWD, nxt, int(a1[i]) - 1, int(a2[i]))
+            nxt = hop
+            if n:
+                nxt = (((hop & u64) + stride) & u64) % n
+                nxt -= (nxt >> 63) << 64
+            field = hop if 0 <= hop < 0xFFFFFFFF else 0xFFFFFFFF
+            outbox.emit_cpu(field, FWD, nxt, int(a1[i]) - 1, int(a2[i]))
     return value, status
 
 

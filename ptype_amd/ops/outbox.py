@@ -66,6 +66,7 @@ class DeviceOutbox:
         if slot >= self.cap:
             b["count"][1] += 1
             return
-        b["actor"][slot] = actor
+        actor &= 0xFFFFFFFF  # the u32 field's bits in the int32 column (0xffffffff -> -1)
+        b["actor"][slot] = actor - (1 << 32) if actor >> 31 else actor
         b["method"][slot] = method
         b["a0"][slot], b["a1"][slot], b["a2"][slot] = a0, a1, a2
